@@ -7,8 +7,22 @@ encode of 1024 objects per GPU, k=4 data + m=2 parity shards of chunk_size =
 inputs resident in HBM, parity written to HBM, through the C ABI
 (mxec_encode_strided_device) on a dedicated HIP stream.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4a|4b|5] [--no-extra] [--no-e2e]
+  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4a|4b|5] [--dump-outputs DIR]
+  python bench.py --full [--no-extra] [--no-e2e] [--cpu-seconds T] ...
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline needs and no more: it builds the batch,
+lets the RS grid tuner decide, runs --warmup steps, times --steps steps and
+prints the line (ms_per_step = wall clock of the timed region / --steps).
+--dump-outputs DIR then writes what the last timed step left in the arrays
+its caller receives (the parity of an encode, the shards of a reconstruct) as
+DIR/<name>.npy, float32, at most 64 MB: whole when small, else a fixed
+seeded sample of 4 KiB chunks (sample_chunks); the inputs are seeded, so two
+builds run with the same arguments can be compared file by file.  --full
+adds everything else described below -- the spot checks against the oracle,
+the host legs, the secondary workloads, the calibration streams, the
+per-kernel breakdowns and the CPU baselines -- whose fields are null in a
+plain run's line.
 
 --gpus N in one process opens ONE mxec_ctx over GPUs 0..N-1 (MaxIO's
 production shape): each GPU gets its own objects (object i -> GPU i mod N,
@@ -18,7 +32,7 @@ the slowest GPU's kernel, with a per-GPU list.  Under torch.distributed.run
 each rank drives GPU LOCAL_RANK and --gpus must equal WORLD_SIZE.  Fewer
 visible GPUs than --gpus: exit 2 with a message and no JSON line
 (BENCH_REHEARSE_LOGICAL=1: a labelled rehearsal on logical devices of one
-card instead).  The default config-2 run also reports extra.e2e_host: the
+card instead).  The config-2 run with --full also reports extra.e2e_host: the
 same encode from page-locked host memory through mxec_encode_batch_host
 (PCIe included) over every GPU of the run.
 
@@ -249,6 +263,11 @@ class Encode:
         for st in self.streams:
             self.main.wait_stream(st)
 
+    def outputs(self):
+        """What the caller of a step receives (--dump-outputs): the parity
+        [n][m][S] (a view of the batch)."""
+        return [("parity", self.parity)]
+
     def spot_check(self):
         """First, middle and last object, and the objects either side of
         every grid-stride iteration boundary of the grid in use, against the
@@ -330,6 +349,11 @@ class Reconstruct:
             pr, expected_ptr=self.dig.data_ptr(), stream=self.sh)
         assert rc == 0, f"reconstruct rc={rc}: {self.ctx.last_error() if hasattr(self.ctx, 'last_error') else ''}"
 
+    def outputs(self):
+        """The objects [n][k+m][S] after the step: the erased shards rebuilt
+        in place beside the present ones."""
+        return [("shards", self.obj)]
+
     def spot_check(self):
         return bool(self.torch.equal(self.obj[self.spot], self.ref))
 
@@ -403,6 +427,9 @@ class ReconstructStream:
                         "readback + decode enqueue); SHA-256 launches of the device's combiner since "
                         "the context opened"}
 
+    def outputs(self):
+        return [(f"shards_w{i}", p.obj) for i, p in enumerate(self.parts)]
+
     def spot_check(self):
         return all(p.spot_check() for p in self.parts)
 
@@ -441,6 +468,7 @@ class Mixed:
         self.streams = [self.main] if streams <= 1 or mode == "batch" else \
             [torch.cuda.Stream(device=dev) for _ in range(streams)]
         rng = np.random.default_rng(seed)
+        g = torch.Generator(device=dev).manual_seed(seed)  # the same bytes from run to run
         kms = [(4, 2), (8, 4), (10, 4)]
         sizes = [64 << 10, 256 << 10, 1 << 20, 4 << 20, 10 << 20]
         self.classes = []  # (k, m, S, n, tensor, data_len, present0)
@@ -449,7 +477,7 @@ class Mixed:
         for (k, m) in kms:
             for S in sizes:
                 n = max(1, per // ((k + m) * S))
-                t = torch.randint(0, 256, (n, k + m, S), dtype=torch.uint8, device=dev)
+                t = torch.randint(0, 256, (n, k + m, S), dtype=torch.uint8, device=dev, generator=g)
                 last = int(rng.integers(1, S))  # short last chunk, zero padded
                 dl = [S] * (k - 1) + [last]
                 pres = np.ones(n * (k + m), np.uint8)
@@ -526,6 +554,11 @@ class Mixed:
             if st is not self.main:
                 self.main.wait_stream(st)
 
+    def outputs(self):
+        """Every class's objects [n][k+m][S] after the step: parity encoded,
+        then the erased shards rebuilt in place."""
+        return [(f"shards_k{k}m{m}_S{S}", t) for (k, m, S, n, t, dl, pres) in self.classes]
+
     def spot_check(self):
         """The last object of every class after the steps: its parity equals
         the oracle's encode of its (short-last-chunk) data."""
@@ -594,6 +627,9 @@ class BodySums:
                 d["us_per_block"] = round(ms * 1e3 / (self.size / 64), 4)
             res[name] = d
         return res
+
+    def outputs(self):
+        return [("sums", self.out)]  # one 76-byte record per body
 
     def spot_check(self):
         import hashlib
@@ -673,6 +709,9 @@ class Frames:
         ok = all(s == 0 for s in status) and bool(torch.equal(self.back[0], self.pt[0]))
         return {"decrypt": {"ms_incl_status_readback": round(ms, 3),
                             "GiBps": round(self.payload / (ms * 1e-3) / GIB, 2), "round_trip_ok": ok}}
+
+    def outputs(self):
+        return [("frames", self.fr)]  # nonce + ciphertext + tag per 64 KiB frame
 
     def spot_check(self):
         oracle = _oracle()
@@ -1396,6 +1435,58 @@ def run_steps(torch, lanes, steps: int, events: bool):
         return list(ex.map(one, lanes))
 
 
+DUMP_BUDGET_ELEMS = 15_000_000  # float32 elements over every file of a run: 60 MB of the 64 MB allowed
+DUMP_CHUNK = 4096
+
+
+def sample_chunks(name: str, rows: int, row_len: int, budget: int):
+    """The fixed sample of a [rows][row_len] output too large to dump whole:
+    (row, offset) of `budget // chunk` chunks of min(row_len, 4096) bytes at
+    positions drawn from a generator seeded by the array's name, any byte
+    offset (tile edges included); the first chunk of the first row and the
+    last of the last row always among them.  Sorted, so two builds write the
+    same chunks in the same order."""
+    import zlib
+
+    import numpy as np
+
+    chunk = min(row_len, DUMP_CHUNK)
+    n = max(2, budget // chunk)
+    rng = np.random.default_rng(SEED + zlib.crc32(name.encode()))
+    r = rng.integers(0, rows, n)
+    c = rng.integers(0, row_len - chunk + 1, n)
+    r[0], c[0], r[1], c[1] = 0, 0, rows - 1, row_len - chunk
+    order = np.lexsort((c, r))
+    return r[order], c[order], chunk
+
+
+def dump_outputs(torch, out_dir: str, lanes, first_gpu: int, n_gpus: int) -> None:
+    """--dump-outputs: every lane's workload.outputs() -- the device arrays a
+    caller of the timed path receives, as the last timed step left them -- to
+    out_dir/<name>.npy as float32 (one file per array, `_gpu<i>` appended when
+    the run has several GPUs).  An array within its share of the budget is
+    written whole in its own shape; a larger one as [chunks][chunk bytes] at
+    sample_chunks' positions."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [(name + (f"_gpu{first_gpu + i}" if n_gpus > 1 else ""), t)
+              for i, (w, _, _) in enumerate(lanes) for name, t in w.outputs()]
+    budget = DUMP_BUDGET_ELEMS // max(1, n_gpus * len(arrays) // max(1, len(lanes)))
+    for name, t in arrays:
+        if t.numel() <= budget:
+            a = t.contiguous().cpu().numpy()
+        else:
+            # rows = the leading dimensions, indexed one by one (the arrays
+            # are strided views of the batch: flattening would copy them)
+            lead = tuple(t.shape[:-1])
+            r, c, chunk = sample_chunks(name, int(np.prod(lead, dtype=np.int64)), t.shape[-1], budget)
+            at = np.stack(np.unravel_index(r, lead), axis=1) if lead else np.zeros((len(r), 0), np.int64)
+            a = torch.stack([t[tuple(int(x) for x in ix)][int(o):int(o) + chunk]
+                             for ix, o in zip(at, c)]).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+
+
 # ---- end-to-end host leg (north_star: PCIe-inclusive rate) -----------------------
 
 
@@ -1910,7 +2001,17 @@ def main() -> int:
                     help="skip the secondary measurements that the default config-2 run adds "
                          "at N=1 (north-star shape, config 3 / 3c, PUT compute)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end host-memory leg")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: spot checks against the oracle, the end-to-end host "
+                         "legs, the secondary workloads (extras), the HBM calibration streams, per-kernel "
+                         "breakdowns and the CPU baselines (--no-extra / --no-e2e / --cpu-seconds trim it); "
+                         "without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of outputs too large for 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
 
@@ -1942,7 +2043,7 @@ def main() -> int:
     one_gpu = plan.n_gpus == 1
     # config 3c (and the default run's extras, which include it) needs one
     # slot per concurrent batch.
-    with_extra = args.config == "2" and one_gpu and not args.no_extra
+    with_extra = args.full and args.config == "2" and one_gpu and not args.no_extra
     ctx = maxio_amd.Context(device_mask=plan.device_mask,
                             streams_per_device=max(2, args.workers if args.config == "3c" or with_extra else 2),
                             test={"logical_devices": plan.logical} if plan.logical > 1 else None)
@@ -1956,7 +2057,7 @@ def main() -> int:
     # chains; the verified GET runs again after the extras
     # (extra.e2e_get_after_extras), which measures that state.
     host_extra = {}
-    if not args.no_e2e and args.config == "2":
+    if args.full and not args.no_e2e and args.config == "2":
         host_extra["e2e_host"] = e2e_host_leg(ctx, torch, plan, 128 if D == 1 and world == 1 else 64)
         if D == 1 and world == 1 and with_extra:
             host_extra["e2e_put_512"] = e2e_put_large(ctx)
@@ -1978,8 +2079,10 @@ def main() -> int:
     tuning = tune_before_timing(torch, lanes, plan.torch_devs)
     run_steps(torch, lanes, args.warmup, events=False)
     sync_all(torch, plan.torch_devs)
-    spot_local = all(bool(l[0].spot_check()) for l in lanes)
-    spot_ok = reduce_max(0.0 if spot_local else 1.0) == 0.0
+    spot_ok = None  # --full: the warmed-up outputs against the oracle
+    if args.full:
+        spot_local = all(bool(l[0].spot_check()) for l in lanes)
+        spot_ok = reduce_max(0.0 if spot_local else 1.0) == 0.0
 
     barrier()
     sync_all(torch, plan.torch_devs)
@@ -1991,6 +2094,8 @@ def main() -> int:
     ms_dev = [sum(a.elapsed_time(b) for a, b in ev) / len(ev) for ev in evs]
     if getattr(w, "wall_timed", False):  # work on the workers' streams, not `stream`
         ms_dev = [elapsed * 1e3 / args.steps] * D
+    if args.dump_outputs:  # before anything below overwrites the buffers
+        dump_outputs(torch, args.dump_outputs, lanes, rank * D, plan.n_gpus)
 
     # The grid the RS grid tuner settled on for the encode shape (0: still
     # tuning), and whether it was the same grid before the timed steps.
@@ -2012,7 +2117,7 @@ def main() -> int:
 
     # §8(d) second denominator: this box's rates for plain streams of the RS
     # kernel's own load/store forms (libmaxio_probe.so), on rank 0's first device.
-    cal = calibrate(torch, dev, stream) if rank == 0 else None
+    cal = calibrate(torch, dev, stream) if rank == 0 and args.full else None
     box_key = {(4, 2): "rs_pattern_k4m2_GBps", (8, 4): "rs_pattern_k8m4_GBps"}.get(
         (getattr(w, "k", 0), getattr(w, "m", 0)), "copy_GBps")
     if isinstance(w, Mixed):
@@ -2032,7 +2137,7 @@ def main() -> int:
     copy_peak = cal.get(box_key) if cal else None
 
     extra = {}
-    if rank == 0 and hasattr(w, "breakdown"):
+    if rank == 0 and args.full and hasattr(w, "breakdown"):
         extra["breakdown"] = w.breakdown()
     if "crc32c" in extra.get("breakdown", {}):
         crc = extra["breakdown"]["crc32c"]
@@ -2041,7 +2146,7 @@ def main() -> int:
         ms_launch = crc["ms"]
         achieved = w.alg_bytes / (ms_launch * 1e-3) / 1e9
         w.kernel = "crc_tiles_kernel + crc_finish_kernel (CRC32C alone)"
-    cpu_spec = w.cpu_work() if (rank == 0 and one_gpu and args.cpu_seconds > 0) else None
+    cpu_spec = w.cpu_work() if (rank == 0 and args.full and one_gpu and args.cpu_seconds > 0) else None
     cpu_sha_ni = getattr(w, "cpu_sha_ni", None)  # set by cpu_work when the baseline hashes
     alg_bytes, w_name, w_kernel, w_bound, w_payload = w.alg_bytes, w.name, w.kernel, w.bound, w.payload
     w_placement = getattr(w, "placement", None)
@@ -2113,6 +2218,7 @@ def main() -> int:
             "n_gpus": plan.n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed * 1e3 / args.steps, 3),
             "higher_is_better": True,
             "scaling": "weak",

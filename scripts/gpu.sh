@@ -6,17 +6,18 @@
 # Steps (each under its own time limit; the first failure ends the call):
 #   tests     full `pytest -m gpu` (one process) -> pytest_gpu.log
 #   smoke     __graft_entry__.smoke()
-#   bench     the driver's command: python bench.py (defaults --gpus 1 --steps 20
-#             --warmup 5) -> bench.json
+#   bench     the whole line: python bench.py --full (defaults --gpus 1 --steps 20
+#             --warmup 5; headline, host legs, extras, calibration, CPU
+#             baselines) -> bench.json
 #   refuse2   python bench.py --gpus 2 on a one-GPU box: must exit 2, no line
 #   rehearse  BENCH_REHEARSE_LOGICAL=1 bench.py --gpus 2 (labelled in-process
 #             multi-device rehearsal on two logical devices of the one card)
 #   rehearse8 the same with --gpus 8 on eight logical devices (64 objects each)
 #   ranks2    the torch.distributed.run path with two ranks on the one GPU
 #             (BENCH_GPU_OF_RANK=0, gloo for the timing collectives)
-#   prof      rocprofv3 --kernel-trace --stats of the default bench command
-#   trace     rocprofv3 --kernel-trace --memory-copy-trace of the default bench
-#             with BENCH_GET_STAMPS=1 and BENCH_DUMP_MAPS=1 (the DSO map on
+#   prof      rocprofv3 --kernel-trace --stats of the bench step's command
+#   trace     rocprofv3 --kernel-trace --memory-copy-trace of the bench step's
+#             command with BENCH_GET_STAMPS=1 and BENCH_DUMP_MAPS=1 (the DSO map on
 #             stderr before teardown); tools/get_trace_summary.py lines the
 #             timed GET batches up with the trace -> get_trace_summary.json
 #   pmc       FETCH_SIZE / WRITE_SIZE passes (one run each) of rs_apply_fast
@@ -27,7 +28,7 @@
 #             3 (SHA-256 split form + decode) and 2 / ns (RS encode):
 #             effective clock per kernel (tools/clock_summary.py)
 #   rust      probe for rustc / cargo
-#   cfg:<c>   python bench.py --config <c> --no-extra -> cfg_<c>.json
+#   cfg:<c>   python bench.py --full --config <c> --no-extra -> cfg_<c>.json
 #   pmc5      FETCH_SIZE / WRITE_SIZE passes over config 5's step (grouped /
 #             multi-r RS launches) -> r6_pmc_cfg5_grouped_traffic.json
 #   exitprobe tools/exit_probe.py host_pageable under rocprofv3 --kernel-trace
@@ -58,28 +59,28 @@ for st in "${STEPS[@]}"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { cat "$O/smoke.log"; exit 1; }
       cat "$O/smoke.log" ;;
     bench)
-      timeout -k 10 900 python bench.py $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+      timeout -k 10 900 python bench.py --full $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
       cat "$O/bench.json" ;;
     refuse2)
       rc=0; timeout -k 10 300 python bench.py --gpus 2 --steps 2 > "$O/refuse2.out" 2> "$O/refuse2.err" || rc=$?
       echo "exit $rc"; cat "$O/refuse2.err"
       [ "$rc" = 2 ] && [ ! -s "$O/refuse2.out" ] || { echo "expected exit 2 and no line"; exit 1; } ;;
     rehearse)
-      BENCH_REHEARSE_LOGICAL=1 timeout -k 10 600 python bench.py --gpus 2 --objects 256 --steps 10 --warmup 2 \
+      BENCH_REHEARSE_LOGICAL=1 timeout -k 10 600 python bench.py --full --gpus 2 --objects 256 --steps 10 --warmup 2 \
         > "$O/rehearse2.json" 2> "$O/rehearse2.err" || { tail -20 "$O/rehearse2.err"; exit 1; }
       cat "$O/rehearse2.json" ;;
     rehearse8)
-      BENCH_REHEARSE_LOGICAL=1 timeout -k 10 600 python bench.py --gpus 8 --objects 64 --steps 10 --warmup 2 \
+      BENCH_REHEARSE_LOGICAL=1 timeout -k 10 600 python bench.py --full --gpus 8 --objects 64 --steps 10 --warmup 2 \
         > "$O/rehearse8.json" 2> "$O/rehearse8.err" || { tail -20 "$O/rehearse8.err"; exit 1; }
       cat "$O/rehearse8.json" ;;
     ranks2)
       BENCH_GPU_OF_RANK=0 BENCH_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 \
-        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --objects 256 --steps 10 \
+        --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --objects 256 --steps 10 \
         --warmup 2 > "$O/ranks2.json" 2> "$O/ranks2.err" || { tail -20 "$O/ranks2.err"; exit 1; }
       cat "$O/ranks2.json" ;;
     prof)
       ( cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats -d /tmp/prof -o run --output-format csv \
-          -- python3 "$R/bench.py" $BENCH_ARGS > "$O/prof_bench.json" 2> "$O/prof_bench.err" ) || { tail -20 "$O/prof_bench.err"; exit 1; }
+          -- python3 "$R/bench.py" --full $BENCH_ARGS > "$O/prof_bench.json" 2> "$O/prof_bench.err" ) || { tail -20 "$O/prof_bench.err"; exit 1; }
       find /tmp/prof -name "*kernel_stats.csv" -exec cp {} "$O/kernel_stats.csv" \;
       find /tmp/prof -name "*kernel_trace.csv" -exec cp {} "$O/kernel_trace.csv" \;
       python tools/headline_timed.py "$O/kernel_trace.csv" "$O/prof_bench.json" --out "$O/headline_timed.json" || exit 1
@@ -87,7 +88,7 @@ for st in "${STEPS[@]}"; do
       cat "$O/prof_bench.json" ;;
     trace)
       ( cd /tmp && BENCH_GET_STAMPS=1 BENCH_DUMP_MAPS=1 timeout -k 10 900 rocprofv3 --kernel-trace --memory-copy-trace -d /tmp/trace \
-          -o run --output-format csv -- python3 "$R/bench.py" $BENCH_ARGS > "$O/trace_bench.json" \
+          -o run --output-format csv -- python3 "$R/bench.py" --full $BENCH_ARGS > "$O/trace_bench.json" \
           2> "$O/trace_bench.err" ) || { tail -20 "$O/trace_bench.err"; exit 1; }
       kt=$(find /tmp/trace -name "*kernel_trace.csv" -print -quit); mt=$(find /tmp/trace -name "*memory_copy_trace.csv" -print -quit)
       python tools/get_trace_summary.py "$kt" "$mt" "$O/trace_bench.json" --out "$O/get_trace_summary.json" > /dev/null \
@@ -168,7 +169,7 @@ for st in "${STEPS[@]}"; do
       [ "$rc" = 0 ] || exit 1 ;;
     cfg:*)
       c="${st#cfg:}"
-      timeout -k 10 900 python bench.py --config "$c" --no-extra $BENCH_ARGS > "$O/cfg_$c.json" 2> "$O/cfg_$c.err" || { tail -20 "$O/cfg_$c.err"; exit 1; }
+      timeout -k 10 900 python bench.py --full --config "$c" --no-extra $BENCH_ARGS > "$O/cfg_$c.json" 2> "$O/cfg_$c.err" || { tail -20 "$O/cfg_$c.err"; exit 1; }
       cat "$O/cfg_$c.json" ;;
     *) echo "unknown step $st"; exit 1 ;;
   esac

@@ -90,6 +90,40 @@ def test_dev_view_binds_device():
     assert calls == [("enc", 5), ("comb", 5), ("close",)]
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a small array is written whole, a large one (a strided
+    view, as the parity is) as the seeded chunk sample -- the same chunks on
+    every run, the array's first and last bytes among them, within the budget."""
+    import numpy as np
+    import torch
+
+    batch = torch.arange(6 * 5 * 1000, dtype=torch.int64).remainder(251).to(torch.uint8).view(6, 5, 1000)
+
+    class W:
+        def outputs(self):
+            return [("small", batch[0, :2, :16]), ("big", batch[:, 3:, :900])]
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_ELEMS", 2 * 1024)
+    monkeypatch.setattr(bench, "DUMP_CHUNK", 64)
+    lanes = [(W(), None, None)]
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / d), lanes, 0, 1)
+    small, big = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert small.dtype == big.dtype == np.float32
+    assert np.array_equal(small, batch[0, :2, :16].numpy())
+    assert big.shape == (16, 64) and small.nbytes + big.nbytes <= 4 * 2 * 1024
+    view = batch[:, 3:, :900].numpy()
+    r, c, chunk = bench.sample_chunks("big", 12, 900, 1024)
+    assert chunk == 64 and (r[0], c[0], r[-1], c[-1]) == (0, 0, 11, 900 - 64)
+    for row, (i, o) in zip(big, zip(r, c)):
+        assert np.array_equal(row, view[i // 2, i % 2, o:o + 64])
+    assert np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))
+    # several GPUs: one file per GPU, the budget shared
+    bench.dump_outputs(torch, str(tmp_path / "c"), lanes, 2, 4)
+    assert sorted(p.name for p in (tmp_path / "c").iterdir()) == ["big_gpu2.npy", "small_gpu2.npy"]
+    assert np.load(tmp_path / "c" / "big_gpu2.npy").shape == (4, 64)
+
+
 def test_blocks_per_cu_mirrors_rs_kernel():
     """bench.rs_blocks_per_cu (the PMC-traffic guard) restates
     rs_default_variant; fail when the kernel's choice moves."""
