@@ -313,6 +313,43 @@ int mxec_encode_batch_device(mxec_ctx* ctx, int dev, void* stream,
                              const uint64_t* data_len,
                              uint8_t* const* parity, uint8_t* digests_dev);
 
+/* ---- ReedSolomon::verify --------------------------------------------------
+ * Recomputes the parity of the data shards on the GPU and compares it with
+ * the stored parity there: (k + m) * shard_size bytes read per object, none
+ * written, no parity downloaded.  A row's result is the lowest byte offset
+ * within the shard at which the stored row differs from the recomputed one,
+ * or MXEC_VERIFY_OK when they agree.  Data shorter than shard_size counts as
+ * zero padded (filesystem.rs:1111) and is not read past its length.
+ * Argument and (k, m) errors are mxec_encode's; m == 0 is
+ * MXEC_E_TOO_FEW_PARITY_SHARDS, as ReedSolomon::new gives. */
+#define MXEC_VERIFY_OK UINT64_MAX
+/* One object in host memory, through mxec_encode's one-request path: the
+ * shards go up, m * 8 bytes come back.  parity[i]: shard_size bytes.
+ * first_bad: m entries, may be NULL.  *consistent (may be NULL): 1 iff every
+ * row matches -- the crate's verify() result. */
+int mxec_verify(mxec_ctx* ctx, int k, int m, size_t shard_size,
+                const uint8_t* const* data, const size_t* data_len,
+                const uint8_t* const* parity, uint64_t* first_bad, int* consistent);
+/* Device-resident batches, laid out as mxec_encode_strided_device /
+ * mxec_encode_batch_device take them; enqueue-only like those.  first_bad_dev
+ * is a device array of n_obj * m (strided) or sum(m) (batch) entries,
+ * object-major, filled on `stream` ahead of the kernel: read it after the
+ * stream has drained.  Objects of a batch that share m share one launch. */
+int mxec_verify_strided_device(mxec_ctx* ctx, int dev, void* stream, int k,
+                               int m, uint64_t shard_size, uint64_t n_obj,
+                               const uint8_t* data, uint64_t data_obj_stride,
+                               uint64_t data_shard_stride,
+                               const uint64_t* data_len, const uint8_t* parity,
+                               uint64_t parity_obj_stride,
+                               uint64_t parity_shard_stride,
+                               uint64_t* first_bad_dev);
+int mxec_verify_batch_device(mxec_ctx* ctx, int dev, void* stream,
+                             const mxec_object* objs, uint64_t n_obj,
+                             const uint8_t* const* data,
+                             const uint64_t* data_len,
+                             const uint8_t* const* parity,
+                             uint64_t* first_bad_dev);
+
 /* End-to-end PUT compute for many objects whose chunks are in HOST memory
  * (request bodies) — the batched form of mxec_encode.  Same array layout as
  * mxec_encode_batch_device but host pointers; digests (host, sum(k+m)) and
@@ -626,6 +663,59 @@ void mxec_reader_close(mxec_reader* r);
 int mxec_try_reconstruct_data_chunk(mxec_ctx* ctx, const char* ec_dir,
                                     uint32_t target, uint8_t* out,
                                     uint64_t out_cap, uint64_t* out_len);
+
+/* ---- scrub / heal of one EC object ---------------------------------------
+ * The reference has no scrubber (no heal-on-read, no background repair): rot
+ * in a shard nobody reads -- parity on every healthy GET -- stays until a
+ * reconstruct needs it.  mxec_scrub_object checks one `{key}.ec` directory
+ * (one stripe: k = chunk_count data shards of chunk_size bytes plus the
+ * manifest's parity shards, as mxec_try_reconstruct_data_chunk treats it)
+ * and can rewrite damaged shards.
+ *   flags   MXEC_SCRUB_PARITY   if every shard file is present with the
+ *                               manifest's size, mxec_verify over them: a
+ *                               cheap first pass that cannot say which shard
+ *                               is at fault; skipped (parity_consistent -1)
+ *                               for an object without parity or with a
+ *                               missing / wrong-sized file;
+ *           MXEC_SCRUB_DIGESTS  SHA-256 of every present shard, parity
+ *                               included, against the manifest;
+ *           MXEC_SCRUB_HEAL     implies DIGESTS; 1 <= damaged <= m: every
+ *                               damaged shard, data and parity, is rebuilt
+ *                               from the verified ones, hashed, and -- only
+ *                               if every rebuilt digest equals the
+ *                               manifest's -- written to a temporary name in
+ *                               ec_dir, fsynced and renamed over its final
+ *                               name.  manifest.json is never rewritten.
+ * Every mode sizes every shard file as the GET path does; a missing or
+ * wrong-sized file is marked in shard_state in every mode.
+ *   verdict MXEC_SCRUB_CLEAN, _DAMAGED (not healed: HEAL not asked), _HEALED,
+ *           or _UNRECOVERABLE (HEAL asked, but more than m shards damaged or
+ *           a rebuilt shard's digest disagrees with the manifest: no file is
+ *           created, changed or removed).
+ * Returns MXEC_OK whenever the scrub itself ran -- damage is reported in
+ * *out, not as an error; manifest, I/O and RS-init errors as from
+ * mxec_get_object_chunked.  Thread-safe: a scrubber may run several objects
+ * from several threads.  `out` points at a mxec_scrub_report. */
+#define MXEC_SCRUB_PARITY 1u
+#define MXEC_SCRUB_DIGESTS 2u
+#define MXEC_SCRUB_HEAL 4u
+#define MXEC_SCRUB_CLEAN 0
+#define MXEC_SCRUB_DAMAGED 1
+#define MXEC_SCRUB_HEALED 2
+#define MXEC_SCRUB_UNRECOVERABLE 3
+#define MXEC_SHARD_OK 0
+#define MXEC_SHARD_MISSING 1
+#define MXEC_SHARD_BAD_SIZE 2
+#define MXEC_SHARD_BAD_DIGEST 3
+#define MXEC_SHARD_HEALED 0x80 /* or-ed into the state of a rewritten shard */
+struct mxec_scrub_report {
+    uint32_t k, m, verdict, n_damaged, n_healed;
+    int32_t parity_consistent; /* 1 / 0, -1 = not checked */
+    uint64_t parity_first_bad; /* lowest mismatching offset over all rows, or MXEC_VERIFY_OK */
+    uint8_t shard_state[256];  /* first k+m entries */
+};
+typedef struct mxec_scrub_report mxec_scrub_report;
+int mxec_scrub_object(mxec_ctx* ctx, const char* ec_dir, uint32_t flags, void* out);
 
 #ifdef __cplusplus
 }

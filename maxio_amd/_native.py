@@ -75,6 +75,21 @@ class MultipartPart(ctypes.Structure):
     ]
 
 
+class ScrubReport(ctypes.Structure):
+    """mxec_scrub_report: what mxec_scrub_object found."""
+
+    _fields_ = [
+        ("k", ctypes.c_uint32),
+        ("m", ctypes.c_uint32),
+        ("verdict", ctypes.c_uint32),
+        ("n_damaged", ctypes.c_uint32),
+        ("n_healed", ctypes.c_uint32),
+        ("parity_consistent", ctypes.c_int32),
+        ("parity_first_bad", ctypes.c_uint64),
+        ("shard_state", ctypes.c_uint8 * 256),
+    ]
+
+
 class Object(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("m", ctypes.c_int32), ("shard_size", ctypes.c_uint64)]
 
@@ -116,6 +131,11 @@ _SIGS = {
     "mxec_encode_strided_device": (
         INT, [P, INT, P, INT, INT, U64, U64, P, U64, U64, U64P, P, U64, U64, P]),
     "mxec_encode_batch_device": (INT, [P, INT, P, ctypes.POINTER(Object), U64, PP, U64P, PP, P]),
+    "mxec_verify": (INT, [P, INT, INT, SZ, PP, SZP, PP, U64P, ctypes.POINTER(INT)]),
+    "mxec_verify_strided_device": (
+        INT, [P, INT, P, INT, INT, U64, U64, P, U64, U64, U64P, P, U64, U64, P]),
+    "mxec_verify_batch_device": (INT, [P, INT, P, ctypes.POINTER(Object), U64, PP, U64P, PP, P]),
+    "mxec_scrub_object": (INT, [P, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(ScrubReport)]),
     "mxec_encode_batch_host": (INT, [P, ctypes.POINTER(Object), U64, PP, U64P, PP, U8P, I32P]),
     "mxec_reconstruct_batch_host": (INT, [P, ctypes.POINTER(Object), U64, PP, U64P, U8P, U8P, ctypes.c_uint32, I32P]),
     "mxec_reconstruct_strided_device": (

@@ -54,6 +54,14 @@ struct RsArgs {
     // Every launch form: at most this many workgroups (0: no cap).  Tests
     // (mxec_open_test rs_grid_cap) shrink the grid so each workgroup walks many tiles.
     uint32_t max_blocks = 0;
+    // Verify launch (ReedSolomon::verify) when set: nothing is written to
+    // out_ptrs -- they are the stored parity rows, read and compared with the
+    // recomputed ones -- and first_bad[o] points at object o's r_total
+    // entries: entry i receives (atomic min) the lowest byte offset at which
+    // stored row i differs, and is left alone when the row agrees.  The
+    // caller fills the entries with 0xFF on the stream ahead of the launch.
+    // Not with `multi`.
+    uint64_t* const* first_bad = nullptr;
 };
 constexpr uint32_t kMultiR = 4;
 

@@ -132,6 +132,8 @@ int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, i
     const size_t o_outlen = w.add(8 * n * r);
     const size_t o_coef = w.add(4 * n);
     const size_t o_edge = w.add(8 * edges.size());
+    const bool verify = objs[0].first_bad != nullptr;
+    const size_t o_fb = verify ? w.add(sizeof(void*) * n) : 0;
     char* hb = w.data();
     auto** ip = reinterpret_cast<const uint8_t**>(hb + o_in);
     auto** op = reinterpret_cast<uint8_t**>(hb + o_out);
@@ -149,6 +151,7 @@ int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, i
             ol[o * r + i] = std::min<uint64_t>(ob.out_len[i], shard_size);
         }
         co[o] = ob.coef_off;
+        if (verify) reinterpret_cast<uint64_t**>(hb + o_fb)[o] = ob.first_bad;
     }
     if (!edges.empty()) std::memcpy(hb + o_edge, edges.data(), 8 * edges.size());
     char* db = nullptr;
@@ -169,11 +172,15 @@ int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, i
     a.r_total = uint32_t(r);
     a.aligned = aligned ? 1u : 0u;
     a.max_blocks = max_blocks ? max_blocks : dev.kn ? dev.kn->test_rs_grid : 0u;
-    if (max_blocks) tune = false;
+    if (verify) a.first_bad = reinterpret_cast<uint64_t* const*>(db + o_fb);
+    if (max_blocks || verify) tune = false;  // the tuner times encodes and decodes only
     // Large aligned single-launch batches take the grid tuner's pick.
     GridTuner::Trial trial;
     const double gb = double(n) * double(k + r) * double(shard_size) / 1e9;
     if (aligned && r <= 4 && tune) MXEC_TRY(rs_grid_pick(dev, k, r, shard_size, gb, &a.blocks_per_cu, &trial));
+    // A verify walks the same tiles as the encode of its shape: the grid the
+    // tuner settled on for that, if it has (0: the default).
+    if (verify && aligned && r <= 4 && !max_blocks) a.blocks_per_cu = uint32_t(rs_grid_in_use(dev, k, r, shard_size));
     hipError_t e = trial.a ? hipEventRecord(trial.a, s) : hipSuccess;
     for (int row0 = 0; row0 < r && e == hipSuccess; row0 += 8) {
         a.row0 = uint32_t(row0);
@@ -322,7 +329,7 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
         int r;
         const std::vector<RsMixedObject>* objs;
         uint64_t sum_k = 0, n_tiles = 0, tile = 0;
-        size_t o_in = 0, o_out = 0, o_inlen = 0, o_outlen = 0, o_coef = 0, o_tiles = 0;
+        size_t o_in = 0, o_out = 0, o_inlen = 0, o_outlen = 0, o_coef = 0, o_tiles = 0, o_fb = 0;
     };
     std::vector<Plan> grouped;
     std::vector<std::pair<int, const std::vector<RsMixedObject>*>> rest;
@@ -380,7 +387,9 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
     // Two or more grouped launches of r <= kMultiR with the same tile: one
     // multi-r launch instead (rs_apply_multi; MXEC_RS_MULTI=0 keeps one
     // launch per r).
-    const bool multi_on = !dev.kn || dev.kn->rs_multi;
+    // A verify call (RsObject::first_bad) runs one launch per r.
+    const bool verify = (*grouped[0].objs)[0].o.first_bad != nullptr;
+    const bool multi_on = !verify && (!dev.kn || dev.kn->rs_multi);
     const uint32_t max_blocks = cap ? cap : dev.kn ? dev.kn->test_rs_grid : 0u;
     bool multi = multi_on && grouped.size() >= 2;
     uint64_t m_obj = 0, m_k = 0, m_tiles = 0;
@@ -459,6 +468,7 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
         p.o_outlen = w.add(8 * n * p.r);
         p.o_coef = w.add(4 * n);
         p.o_tiles = w.add(sizeof(RsTileRec) * p.n_tiles);
+        if (verify) p.o_fb = w.add(sizeof(void*) * n);
     }
     char* hb = w.data();
     for (const Plan& p : grouped) {
@@ -481,6 +491,7 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
                 ol[o * r + i] = std::min<uint64_t>(ob.o.out_len[i], ob.shard_size);
             }
             co[o] = ob.o.coef_off;
+            if (verify) reinterpret_cast<uint64_t**>(hb + p.o_fb)[o] = ob.o.first_bad;
             const uint64_t nt = (ob.shard_size + p.tile - 1) / p.tile;
             for (uint64_t t = 0; t < nt; ++t)
                 tr[t0 + t] = RsTileRec{uint32_t(o), uint32_t(ob.k), uint32_t(in0), uint32_t(t)};
@@ -505,6 +516,7 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
         a.tiles = reinterpret_cast<const RsTileRec*>(db + p.o_tiles);
         a.n_tiles = p.n_tiles;
         a.max_blocks = max_blocks;
+        if (verify) a.first_bad = reinterpret_cast<uint64_t* const*>(db + p.o_fb);
         MXEC_HIP(launch_rs_apply(a, dev.n_cus, s));
     }
     return w.finish(s);

@@ -23,6 +23,12 @@ struct RsObject {
     uint8_t* const* out;       // r
     const uint64_t* out_len;   // r
     uint32_t coef_off;         // dword offset of this object's [j][i][8] table
+    // Verify (ReedSolomon::verify) when set, for every object of the call or
+    // none: `out` are the stored parity rows, read and compared with the
+    // recomputed ones, never written; first_bad (device, r entries, filled
+    // with 0xFF on the stream ahead of the call) receives per row the lowest
+    // byte offset at which they differ (kernels.hpp RsArgs::first_bad).
+    uint64_t* first_bad = nullptr;
 };
 
 // Applies each object's matrix; all objects share (k, r, shard_size).

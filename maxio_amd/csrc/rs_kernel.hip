@@ -27,6 +27,9 @@
 //    in the same pass.  Launches with an unaligned pointer run the
 //    byte-exact edge kernel over every tile instead (a per-launch tile list
 //    built by the host, run_rs).
+//  * ReedSolomon::verify is the same walk with the stores replaced by a
+//    compare against the stored parity (rs_tile's CMP policy, rs_verify_*):
+//    (k + r) x S bytes read, none written.
 #include "kernels.hpp"
 
 #include <cstdlib>
@@ -168,16 +171,57 @@ __device__ __forceinline__ void gstore16(gptr p, const uint32_t (&w)[4]) {
     else *q = v;
 }
 
+// Inputs and outputs that a length boundary cuts inside a tile (the short
+// last data chunk, its decoded copy, a shard end that is not a tile
+// multiple).  `valid` is a lane's count of bytes below the length from the
+// start of its 16-byte vector (<= 0: none, >= 16: all).  A vector with at
+// least one valid byte is loaded whole -- it is 16-byte aligned, so it lies
+// in the page of its first byte -- and the bytes at or past the length are
+// zeroed; a vector with none reads a safe dummy address, so every load
+// stays unconditional and counted.
+__device__ __forceinline__ Vec4 mask_tail(Vec4 x, int32_t valid) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int32_t nb = valid - 4 * w;
+        const uint32_t mk = nb >= 4 ? 0xFFFFFFFFu : (nb <= 0 ? 0u : (0xFFFFFFFFu >> (32 - 8 * nb)));
+        x.w[w] &= mk;
+    }
+    return x;
+}
+
+// Verify launches (RsArgs::first_bad set) compare instead of storing: the
+// "outputs" are the stored parity, read like the encode would write it, and
+// a row's result is the lowest byte offset at which it differs from the
+// accumulators.  diff: this lane's 16 bytes of (recomputed ^ stored), zero
+// where they agree or past the length; off: their offset in the shard.
+// Lanes of a wave hold ascending offsets, so the wave's lowest mismatch is
+// in the lowest lane of the ballot; that lane alone takes the atomic.  A
+// wave without a mismatch (every wave of a clean stripe) writes nothing.
+__device__ __forceinline__ uint32_t any_bits(const uint32_t (&d)[4]) { return d[0] | d[1] | d[2] | d[3]; }
+
+__device__ __forceinline__ void report_first_bad(uint64_t* const* __restrict__ fbp, uint32_t row,
+                                                 const uint32_t (&d)[4], uint64_t off) {
+    const uint64_t bad = __builtin_amdgcn_ballot_w64(any_bits(d) != 0);
+    if (bad == 0) return;
+    if ((threadIdx.x & 63u) != uint32_t(__builtin_ctzll(bad))) return;
+    // Its first non-zero dword (selects: no indexed register access).
+    const uint32_t w = d[0] ? 0u : d[1] ? 1u : d[2] ? 2u : 3u;
+    const uint32_t x = d[0] ? d[0] : d[1] ? d[1] : d[2] ? d[2] : d[3];
+    const uint64_t at = off + 4 * w + (uint32_t(__builtin_ctz(x)) >> 3);
+    atomicMin(reinterpret_cast<unsigned long long*>(*fbp + row), static_cast<unsigned long long>(at));
+}
+
 // Edge tiles (launches with an unaligned pointer): the list entries
 // (object << 32 | tile index) are every tile of every object.  Each is walked in kEdgeTile steps with
 // byte-exact bounds on every input and output.  One step:
-template <int R>
+template <int R, bool CMP = false>
 __device__ __forceinline__ void edge_step(
     const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
     const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint64_t shard_size,
     uint32_t k, uint32_t r_total, uint32_t row0, const uint64_t* __restrict__ edge_list,
-    uint32_t steps_per_tile, uint64_t tile_bytes, uint32_t aligned, uint64_t step) {
+    uint32_t steps_per_tile, uint64_t tile_bytes, uint32_t aligned, uint64_t step,
+    uint64_t* const* __restrict__ fb_ptrs = nullptr) {
     const uint64_t e = edge_list[step / steps_per_tile];
     const uint32_t obj = uint32_t(e >> 32);
     const uint64_t col = uint64_t(uint32_t(e)) * tile_bytes + (step % steps_per_tile) * kEdgeTile +
@@ -234,7 +278,15 @@ __device__ __forceinline__ void edge_step(
     for (int i = 0; i < R; ++i) {
         uint64_t olen = out_len[uint64_t(obj) * r_total + row0 + i];
         if (olen > shard_size) olen = shard_size;
-        if (col < olen) {
+        if constexpr (CMP) {
+            // The stored row's bytes below its length against the accumulators.
+            const int64_t valid = col < olen ? int64_t(olen - col) : 0;
+            Vec4 st{{0, 0, 0, 0}};
+            if (valid > 0) st = load_partial(out_ptrs[uint64_t(obj) * r_total + row0 + i] + col, valid, aligned != 0);
+            Vec4 df{{acc[0][0][i] ^ st.w[0], acc[0][1][i] ^ st.w[1], acc[0][2][i] ^ st.w[2], acc[0][3][i] ^ st.w[3]}};
+            df = mask_tail(df, valid >= 16 ? 16 : int32_t(valid));
+            report_first_bad(fb_ptrs + obj, row0 + i, df.w, col);
+        } else if (col < olen) {
             uint32_t o[4] = {acc[0][0][i], acc[0][1][i], acc[0][2][i], acc[0][3][i]};
             store_partial(out_ptrs[uint64_t(obj) * r_total + row0 + i] + col, o, int64_t(olen - col),
                           aligned != 0);
@@ -255,22 +307,18 @@ __global__ __launch_bounds__(kThreads) void rs_apply_edge(
                      steps_per_tile, tile_bytes, aligned, step);
 }
 
-// Inputs and outputs that a length boundary cuts inside a tile (the short
-// last data chunk, its decoded copy, a shard end that is not a tile
-// multiple).  `valid` is a lane's count of bytes below the length from the
-// start of its 16-byte vector (<= 0: none, >= 16: all).  A vector with at
-// least one valid byte is loaded whole -- it is 16-byte aligned, so it lies
-// in the page of its first byte -- and the bytes at or past the length are
-// zeroed; a vector with none reads a safe dummy address, so every load
-// stays unconditional and counted.
-__device__ __forceinline__ Vec4 mask_tail(Vec4 x, int32_t valid) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const int32_t nb = valid - 4 * w;
-        const uint32_t mk = nb >= 4 ? 0xFFFFFFFFu : (nb <= 0 ? 0u : (0xFFFFFFFFu >> (32 - 8 * nb)));
-        x.w[w] &= mk;
-    }
-    return x;
+// The same walk for a verify launch: out_ptrs are the stored parity rows.
+template <int R>
+__global__ __launch_bounds__(kThreads) void rs_verify_edge(
+    const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
+    const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
+    const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint64_t shard_size,
+    uint32_t k, uint32_t r_total, uint32_t row0, const uint64_t* __restrict__ edge_list,
+    uint32_t steps_per_tile, uint64_t tile_bytes, uint32_t aligned, uint64_t n_steps,
+    uint64_t* const* __restrict__ fb_ptrs) {
+    for (uint64_t step = blockIdx.x; step < n_steps; step += gridDim.x)
+        edge_step<R, true>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, shard_size, k, r_total, row0,
+                           edge_list, steps_per_tile, tile_bytes, aligned, step, fb_ptrs);
 }
 
 template <bool NT>
@@ -286,12 +334,15 @@ __device__ __forceinline__ Vec4 gload16_upto(gcptr p, int32_t valid, gcptr safe)
 // object: a quarter of all tiles at 64 KiB chunks).  ip / il: the object's
 // k inputs and lengths; op / ol: its R outputs and lengths; tab: its
 // coefficient table at the first output row, input j's rows `stride` x 8
-// dwords apart.
-template <int R, int V, bool NT, bool LNT = NT, int G = 4>
+// dwords apart.  CMP (verify launches): op are the stored rows, compared
+// with the accumulators instead of written; fbp points at the object's
+// first_bad pointer, `row` is the index of its first row there.
+template <int R, int V, bool NT, bool LNT = NT, int G = 4, bool CMP = false>
 __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, const uint64_t* __restrict__ il,
                                         uint8_t* const* __restrict__ op, const uint64_t* __restrict__ ol,
                                         const uint32_t* __restrict__ tab, uint32_t k, uint32_t stride,
-                                        uint64_t base, gcptr safe) {
+                                        uint64_t base, gcptr safe, uint64_t* const* __restrict__ fbp = nullptr,
+                                        uint32_t row = 0) {
     constexpr uint32_t kTile = kThreads * 16 * V;
     const uint64_t end = base + kTile;
     const uint64_t lane = base + threadIdx.x * 16;
@@ -387,6 +438,61 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
         load_in(j, x);
         mac_column<R, V>(acc, x, tab + j * stride * 8);
     }
+    if constexpr (CMP) {
+        // Every row's stored vectors in flight at once (the inputs'
+        // registers are free by now), cut at the row's length like the
+        // encode's stores; then one ballot per row and vector.  A row that
+        // ends at or before the tile has nothing stored here.
+        Vec4 st[R][V];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const uint64_t olen = ol[i];
+            gcptr o = ((gcptr)(op[i])) + lane;
+            if (olen >= end) {
+#pragma unroll
+                for (int v = 0; v < V; ++v) st[i][v] = gload16<LNT>(o + v * kThreads * 16);
+            } else if (olen <= base) {
+#pragma unroll
+                for (int v = 0; v < V; ++v)
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) st[i][v].w[w] = acc[v][w][i];
+            } else {
+                const int32_t d = int32_t(olen - base) - lane_off;
+#pragma unroll
+                for (int v = 0; v < V; ++v) {
+                    const int32_t valid = d - v * int32_t(kThreads * 16);
+                    // Masked after the XOR: past the length the two agree.
+                    st[i][v] = gload16<LNT>(valid > 0 ? o + v * kThreads * 16 : safe);
+                    if (valid < 16) {
+                        Vec4 a{{acc[v][0][i], acc[v][1][i], acc[v][2][i], acc[v][3][i]}};
+                        const Vec4 keep = mask_tail(Vec4{{~0u, ~0u, ~0u, ~0u}}, valid);
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) st[i][v].w[w] = (st[i][v].w[w] & keep.w[w]) | (a.w[w] & ~keep.w[w]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            uint32_t df[V][4], any = 0;
+#pragma unroll
+            for (int v = 0; v < V; ++v)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    df[v][w] = acc[v][w][i] ^ st[i][v].w[w];
+                    any |= df[v][w];
+                }
+            if (__builtin_amdgcn_ballot_w64(any != 0) == 0) continue;  // the common case
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                // Vector v of every lane lies below vector v + 1 of any lane.
+                if (__builtin_amdgcn_ballot_w64(any_bits(df[v]) != 0) == 0) continue;
+                report_first_bad(fbp, row + uint32_t(i), df[v], lane + uint64_t(v) * kThreads * 16);
+                break;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         const uint64_t olen = ol[i];
@@ -419,13 +525,13 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
 // the object), one wave-uniform scalar load, fetched one tile ahead so it
 // is in SGPRs when the tile starts (the uniform kernel computes the same
 // from the tile index).
-template <int R, int V, bool NT, bool GRP, int OCC = 1, bool LNT = NT, int G = 4>
-__global__ __launch_bounds__(kThreads, OCC) void rs_apply_fast(
+template <int R, int V, bool NT, bool GRP, bool LNT, int G, bool CMP>
+__device__ __forceinline__ void fast_tiles(
     const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
     const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
     uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
-    const RsTileRec* __restrict__ tiles) {
+    const RsTileRec* __restrict__ tiles, uint64_t* const* __restrict__ fb_ptrs) {
     constexpr uint32_t kTile = kThreads * 16 * V;
     const gcptr safe = (gcptr)(reinterpret_cast<const uint8_t*>(coef));
     RsTileRec next{};
@@ -448,10 +554,36 @@ __global__ __launch_bounds__(kThreads, OCC) void rs_apply_fast(
         }
         // Lengths are clamped to the shard size by the host, so a tile past
         // the shard end is cut by the same tests.
-        rs_tile<R, V, NT, LNT, G>(in_ptrs + in0, in_len + in0, out_ptrs + uint64_t(obj) * r_total + row0,
-                          out_len + uint64_t(obj) * r_total + row0, coef + coef_off[obj] + row0 * 8, k, r_total,
-                          base, safe);
+        rs_tile<R, V, NT, LNT, G, CMP>(in_ptrs + in0, in_len + in0, out_ptrs + uint64_t(obj) * r_total + row0,
+                                       out_len + uint64_t(obj) * r_total + row0, coef + coef_off[obj] + row0 * 8, k,
+                                       r_total, base, safe, CMP ? fb_ptrs + obj : nullptr, row0);
     }
+}
+
+template <int R, int V, bool NT, bool GRP, int OCC = 1, bool LNT = NT, int G = 4>
+__global__ __launch_bounds__(kThreads, OCC) void rs_apply_fast(
+    const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
+    const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
+    const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
+    uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
+    const RsTileRec* __restrict__ tiles) {
+    fast_tiles<R, V, NT, GRP, LNT, G, false>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform, r_total,
+                                             row0, tiles_per_obj, n_tiles, tiles, nullptr);
+}
+
+// ReedSolomon::verify: the encode's walk with the compare in place of the
+// stores (rs_tile CMP).  out_ptrs are the stored parity rows, fb_ptrs[o]
+// object o's r_total first_bad entries (filled with 0xFF by the host before
+// the launch).  Reads (k + r) x S bytes per object and writes none.
+template <int R, int V, bool GRP>
+__global__ __launch_bounds__(kThreads) void rs_verify_fast(
+    const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
+    const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
+    const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
+    uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
+    const RsTileRec* __restrict__ tiles, uint64_t* const* __restrict__ fb_ptrs) {
+    fast_tiles<R, V, true, GRP, true, 4, true>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform,
+                                               r_total, row0, tiles_per_obj, n_tiles, tiles, fb_ptrs);
 }
 
 // One grouped launch for objects of every output count r <= kMultiR (a
@@ -506,6 +638,16 @@ hipError_t launch_fast(const RsArgs& a, uint32_t tiles_per_obj, uint64_t n_tiles
     return hipGetLastError();
 }
 
+// Verify launches (a.first_bad set): the shipping geometry of the same R.
+template <int R, int V, bool GRP>
+hipError_t launch_verify(const RsArgs& a, uint32_t tiles_per_obj, uint64_t n_tiles, uint64_t blocks,
+                         hipStream_t s) {
+    hipLaunchKernelGGL((rs_verify_fast<R, V, GRP>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
+                       a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
+                       tiles_per_obj, n_tiles, a.tiles, a.first_bad);
+    return hipGetLastError();
+}
+
 // Multi-r grouped launches (a.multi): V = 4, nontemporal, rs_group_variant's grid.
 hipError_t launch_multi(const RsArgs& a, int n_cus, hipStream_t s) {
     const RsVariant v = rs_group_variant(kMultiR);
@@ -520,6 +662,12 @@ template <int R>
 hipError_t launch_grouped(const RsArgs& a, int n_cus, hipStream_t s) {
     const RsVariant v = rs_group_variant(uint32_t(R));
     const uint64_t blocks = grid_of(a, n_cus, v.blocks_per_cu, a.n_tiles);
+    if (a.first_bad) {
+        if constexpr (R <= 4) {
+            if (v.vecs == 4) return launch_verify<R, 4, true>(a, 0, a.n_tiles, blocks, s);
+        }
+        return launch_verify<R, 2, true>(a, 0, a.n_tiles, blocks, s);
+    }
     if constexpr (R <= 4) {
         if (v.vecs == 4) return launch_fast<R, 4, true, true>(a, 0, a.n_tiles, blocks, s);
     }
@@ -534,6 +682,13 @@ hipError_t launch_r(const RsArgs& a, int n_cus, hipStream_t s, const RsVariant& 
         const uint64_t n_tiles = uint64_t(tiles_per_obj) * a.n_obj;
         const uint64_t blocks = grid_of(a, n_cus, var.blocks_per_cu, n_tiles);
         hipError_t e = hipErrorInvalidValue;
+        if (a.first_bad) {  // verify: the shipping geometries only
+            if constexpr (R <= 4) {
+                if (var.vecs == 4) return launch_verify<R, 4, false>(a, tiles_per_obj, n_tiles, blocks, s);
+            }
+            if (var.vecs == 2) return launch_verify<R, 2, false>(a, tiles_per_obj, n_tiles, blocks, s);
+            return e;
+        }
         if (var.nt && var.load_nt && var.store_nt && var.group == 4 && var.min_waves == 0) {
             // The shipping geometries (rs_default_variant): V = 4 while the
             // accumulators fit (R <= 4), V = 2 beyond.
@@ -564,6 +719,13 @@ hipError_t launch_r(const RsArgs& a, int n_cus, hipStream_t s, const RsVariant& 
         const uint32_t steps = uint32_t(tile / kEdgeTile);
         const uint64_t n_steps = a.n_edge * steps;
         const uint64_t blocks = grid_of(a, n_cus, 8, n_steps);
+        if (a.first_bad) {
+            hipLaunchKernelGGL((rs_verify_edge<R>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s,
+                               a.in_ptrs, a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off,
+                               a.shard_size, a.k, a.r_total, a.row0, a.edge_list, steps, tile, a.aligned,
+                               n_steps, a.first_bad);
+            return hipGetLastError();
+        }
         hipLaunchKernelGGL((rs_apply_edge<R>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s,
                            a.in_ptrs, a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off,
                            a.shard_size, a.k, a.r_total, a.row0, a.edge_list, steps, tile, a.aligned,
@@ -666,7 +828,7 @@ hipError_t launch_rs_apply_variant(const RsArgs& a, int n_cus, hipStream_t s, co
 
 hipError_t launch_rs_apply(const RsArgs& a, int n_cus, hipStream_t s) {
     if (a.tiles && a.multi) {
-        if (!a.aligned || a.row0 != 0) return hipErrorInvalidValue;
+        if (!a.aligned || a.row0 != 0 || a.first_bad) return hipErrorInvalidValue;  // no multi-r verify
         if (a.n_tiles == 0) return hipSuccess;
         return launch_multi(a, n_cus, s);
     }

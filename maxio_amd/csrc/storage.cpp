@@ -17,6 +17,8 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +38,7 @@
 #include "manifest.hpp"
 #include "ops.hpp"
 #include "runtime.hpp"
+#include "scrub_plan.hpp"
 
 namespace fs = std::filesystem;
 using mxec::set_error;
@@ -634,6 +637,168 @@ int mxec_put_object_chunked_sums(mxec_ctx* ctx, const char* ec_dir, uint64_t chu
 }
 
 }  // extern "C"
+
+// ---- scrub / heal ------------------------------------------------------------
+
+namespace {
+
+// A rebuilt shard under its final name, all of it or not at all: written to
+// a temporary name in the same directory, fsynced, renamed over the final
+// name, and the directory entry fsynced.
+int replace_file(const fs::path& dir, const std::string& name, const uint8_t* data, size_t len) {
+    static std::atomic<uint64_t> seq{0};
+    const fs::path tmp = dir / ("." + name + ".heal." + std::to_string(::getpid()) + "." + std::to_string(seq++));
+    const int fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_EXCL | O_CLOEXEC, 0644);
+    if (fd < 0) return set_error(MXEC_E_IO, "IO error: cannot create " + tmp.string() + ": " + std::strerror(errno));
+    size_t put = 0;
+    while (put < len) {
+        const ssize_t w = ::write(fd, data + put, len - put);
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) break;
+        put += size_t(w);
+    }
+    bool ok = put == len && ::fsync(fd) == 0;
+    ok = (::close(fd) == 0) && ok;
+    if (ok && ::rename(tmp.c_str(), (dir / name).c_str()) != 0) ok = false;
+    if (!ok) {
+        const std::string why = std::strerror(errno);
+        ::unlink(tmp.c_str());
+        return set_error(MXEC_E_IO, "IO error: heal write failed for " + (dir / name).string() + ": " + why);
+    }
+    const int dfd = ::open(dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
+    if (dfd >= 0) {
+        (void)::fsync(dfd);
+        ::close(dfd);
+    }
+    return MXEC_OK;
+}
+
+int scrub_object(mxec_ctx* ctx, const fs::path& dir, uint32_t flags, mxec_scrub_report* rep) {
+    if (flags & MXEC_SCRUB_HEAL) flags |= MXEC_SCRUB_DIGESTS;
+    Manifest man;
+    MXEC_TRY(read_manifest(dir, man));
+    const int k = int(man.chunk_count);
+    const int m = man.has_parity ? int(man.parity_shards) : 0;
+    const uint64_t shard = man.has_shard ? man.shard_size : man.chunk_size;
+    if (m > 0) {  // an object without parity has nothing ReedSolomon::new would see
+        const int rc = mxec_rs_check(k, m);
+        if (rc) return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
+    }
+    const int total = k + m;
+    if (total > int(sizeof rep->shard_state))
+        return set_error(MXEC_E_INVALID_ARG, "scrub: more shards than the report holds (" + std::to_string(total) + ")");
+    if (int(man.chunks.size()) < total) return set_error(MXEC_E_JSON, "JSON error: manifest lists fewer shards than k+m");
+    rep->k = uint32_t(k);
+    rep->m = uint32_t(m);
+
+    // Every shard file, parity included, read and sized as reconstruct_from_dir does.
+    std::vector<Bytes> bufs(static_cast<size_t>(total));
+    std::vector<uint8_t*> ptrs(static_cast<size_t>(total));
+    std::vector<size_t> lens(static_cast<size_t>(total));
+    uint8_t* st = rep->shard_state;
+    for (int i = 0; i < total; ++i) {
+        const size_t want = size_t(i < k ? std::min<uint64_t>(man.chunks[size_t(i)].size, shard) : shard);
+        Bytes& b = bufs[size_t(i)];
+        if (read_file(dir / chunk_name(uint32_t(i)), b) != MXEC_OK) st[i] = MXEC_SHARD_MISSING;
+        else if (b.size() != want) st[i] = MXEC_SHARD_BAD_SIZE;
+        if (st[i] != MXEC_SHARD_OK) b.assign(want, 0);  // where a heal rebuilds it
+        lens[size_t(i)] = want;
+        ptrs[size_t(i)] = b.data();
+    }
+    set_error(0, "");  // a missing file is a finding, not this call's error
+
+    if ((flags & MXEC_SCRUB_PARITY) && m > 0 && mxec::scrub_damaged(st, uint32_t(total)) == 0) {
+        std::vector<uint64_t> fb(static_cast<size_t>(m));
+        int ok = 0;
+        MXEC_TRY(mxec_verify(ctx, k, m, shard, ptrs.data(), lens.data(), ptrs.data() + k, fb.data(), &ok));
+        rep->parity_consistent = ok;
+        for (uint64_t v : fb) rep->parity_first_bad = std::min(rep->parity_first_bad, v);
+    }
+
+    std::vector<uint8_t> expected(size_t(total) * 32, 0);
+    std::vector<uint8_t> parsed(static_cast<size_t>(total), 0);
+    if (flags & MXEC_SCRUB_DIGESTS) {
+        std::vector<const uint8_t*> hp;
+        std::vector<size_t> hl;
+        std::vector<int> hi;
+        for (int i = 0; i < total; ++i) {
+            parsed[size_t(i)] = unhex32(man.chunks[size_t(i)].sha256, &expected[size_t(i) * 32]);
+            if (st[i] != MXEC_SHARD_OK) continue;
+            if (!parsed[size_t(i)]) {  // a digest that does not parse can never match
+                st[i] = MXEC_SHARD_BAD_DIGEST;
+                continue;
+            }
+            hp.push_back(lens[size_t(i)] ? ptrs[size_t(i)] : reinterpret_cast<const uint8_t*>(""));
+            hl.push_back(lens[size_t(i)]);
+            hi.push_back(i);
+        }
+        std::vector<uint8_t> dig(hp.size() * 32);
+        MXEC_TRY(mxec_sha256_batch(ctx, hp.data(), hl.data(), hp.size(), reinterpret_cast<uint8_t(*)[32]>(dig.data())));
+        for (size_t t = 0; t < hi.size(); ++t)
+            if (std::memcmp(&dig[t * 32], &expected[size_t(hi[t]) * 32], 32) != 0) st[hi[t]] = MXEC_SHARD_BAD_DIGEST;
+    }
+
+    rep->n_damaged = mxec::scrub_damaged(st, uint32_t(total));
+    bool rebuilt_ok = false;
+    if ((flags & MXEC_SCRUB_HEAL) && mxec::scrub_can_heal(rep->n_damaged, uint32_t(m))) {
+        // Every damaged shard, data and parity, from the verified ones (the
+        // digests were checked above, so the decode takes the mask as it is).
+        std::vector<uint8_t> present(static_cast<size_t>(total));
+        std::vector<int> bad;
+        for (int i = 0; i < total; ++i) {
+            present[size_t(i)] = st[i] == MXEC_SHARD_OK;
+            if (!present[size_t(i)]) {
+                bad.push_back(i);
+                bufs[size_t(i)].assign(lens[size_t(i)], 0);
+                ptrs[size_t(i)] = bufs[size_t(i)].data();
+            }
+        }
+        // A zero-length shard has no buffer of its own; the decode wants a pointer.
+        uint8_t none = 0;
+        for (int i = 0; i < total; ++i)
+            if (!ptrs[size_t(i)]) ptrs[size_t(i)] = &none;
+        int np = 0;
+        MXEC_TRY(mxec_reconstruct(ctx, k, m, shard, ptrs.data(), lens.data(), nullptr, present.data(), 0, &np));
+        // Written only if every rebuilt shard is what the manifest recorded.
+        std::vector<const uint8_t*> hp;
+        std::vector<size_t> hl;
+        for (int i : bad) {
+            hp.push_back(ptrs[size_t(i)]);
+            hl.push_back(lens[size_t(i)]);
+        }
+        std::vector<uint8_t> dig(hp.size() * 32);
+        MXEC_TRY(mxec_sha256_batch(ctx, hp.data(), hl.data(), hp.size(), reinterpret_cast<uint8_t(*)[32]>(dig.data())));
+        rebuilt_ok = true;
+        for (size_t t = 0; t < bad.size(); ++t)
+            rebuilt_ok = rebuilt_ok && parsed[size_t(bad[t])] &&
+                         std::memcmp(&dig[t * 32], &expected[size_t(bad[t]) * 32], 32) == 0;
+        if (rebuilt_ok) {
+            for (int i : bad) {
+                MXEC_TRY(replace_file(dir, chunk_name(uint32_t(i)), ptrs[size_t(i)], lens[size_t(i)]));
+                st[i] |= MXEC_SHARD_HEALED;
+                ++rep->n_healed;
+            }
+        }
+    }
+    rep->verdict = mxec::scrub_verdict(rep->n_damaged, uint32_t(m), rep->parity_consistent,
+                                       (flags & MXEC_SCRUB_HEAL) != 0, rebuilt_ok);
+    return MXEC_OK;
+}
+
+}  // namespace
+
+extern "C" int mxec_scrub_object(mxec_ctx* ctx, const char* ec_dir, uint32_t flags, void* out) {
+    return mxec::guarded([&]() -> int {
+        if (!ec_dir || !out) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        if (flags & ~(MXEC_SCRUB_PARITY | MXEC_SCRUB_DIGESTS | MXEC_SCRUB_HEAL))
+            return set_error(MXEC_E_INVALID_ARG, "scrub: unknown flag");
+        auto* rep = static_cast<mxec_scrub_report*>(out);
+        std::memset(rep, 0, sizeof *rep);
+        rep->parity_consistent = -1;
+        rep->parity_first_bad = MXEC_VERIFY_OK;
+        return scrub_object(ctx, fs::path(ec_dir), flags, rep);
+    });
+}
 
 // ---- VerifiedChunkReader (chunk_reader.rs:12-276) --------------------------
 

@@ -51,6 +51,11 @@ DATA_ONLY = 0x1
 # mxec_body_sums_batch flags (include/maxio_ec.h MXEC_SUM_*)
 SUM_MD5, SUM_CRC32, SUM_CRC32C, SUM_SHA1, SUM_SHA256 = 0x01, 0x02, 0x04, 0x08, 0x10
 FRAME_CHUNK_SIZE = 65536  # crypto.rs:46
+# mxec_verify / mxec_scrub_object (include/maxio_ec.h MXEC_VERIFY_OK, MXEC_SCRUB_*, MXEC_SHARD_*)
+VERIFY_OK = (1 << 64) - 1
+SCRUB_PARITY, SCRUB_DIGESTS, SCRUB_HEAL = 1, 2, 4
+SCRUB_CLEAN, SCRUB_DAMAGED, SCRUB_HEALED, SCRUB_UNRECOVERABLE = 0, 1, 2, 3
+SHARD_OK, SHARD_MISSING, SHARD_BAD_SIZE, SHARD_BAD_DIGEST, SHARD_HEALED = 0, 1, 2, 3, 0x80
 _SUM_BY_ALGO = {"CRC32": SUM_CRC32, "CRC32C": SUM_CRC32C, "SHA1": SUM_SHA1, "SHA256": SUM_SHA256}
 
 
@@ -290,6 +295,24 @@ class Context:
             dig.ctypes.data_as(N.U8P) if digests else None))
         return parity, ([bytes(dig[i]) for i in range(k + m)] if digests else None)
 
+    def verify(self, data: Sequence, parity: Sequence, shard_size: int):
+        """ReedSolomon::verify on the GPU (mxec_verify): returns (consistent,
+        first_bad) -- per parity row the lowest byte offset at which the
+        stored row differs from the recomputed one, VERIFY_OK where they
+        agree.  Data chunks shorter than shard_size count as zero padded."""
+        arrs = [_u8(d) for d in data]
+        par = [_u8(p) for p in parity]
+        for p in par:
+            if p.size != shard_size:
+                raise RSError(-9, "parity shard is not shard_size bytes")
+        k, m = len(arrs), len(par)
+        fb = np.zeros(max(1, m), np.uint64)
+        ok = ctypes.c_int(0)
+        _check(self._lib.mxec_verify(
+            self._h, k, m, shard_size, _pp([_ptr(a) for a in arrs]), _szp([a.size for a in arrs]),
+            _pp([_ptr(p) for p in par]), fb.ctypes.data_as(N.U64P), ctypes.byref(ok)))
+        return bool(ok.value), [int(v) for v in fb[:m]]
+
     def reconstruct(self, shards: Sequence[Optional[object]], k: int, m: int, shard_size: int,
                     shard_len: Optional[Sequence[int]] = None,
                     expected: Optional[Sequence[bytes]] = None, data_only: bool = False):
@@ -401,6 +424,26 @@ class Context:
         pp = parity_ptrs if isinstance(parity_ptrs, ctypes.Array) else _pp(parity_ptrs)
         dl = None if data_len is None else (data_len if isinstance(data_len, ctypes.Array) else _u64p(data_len))
         _check(self._lib.mxec_encode_batch_device(self._h, dev, stream, arr, len(objs), dp, dl, pp, digests_ptr))
+
+    def verify_strided_device(self, k, m, shard_size, n_obj, data_ptr, data_obj_stride,
+                              data_shard_stride, parity_ptr, parity_obj_stride, parity_shard_stride,
+                              first_bad_ptr, data_len=None, dev=0, stream=None):
+        """mxec_verify_strided_device: enqueue-only; first_bad_ptr is a device
+        array of n_obj * m uint64, read after the stream has drained."""
+        _check(self._lib.mxec_verify_strided_device(
+            self._h, dev, stream, k, m, shard_size, n_obj, data_ptr, data_obj_stride,
+            data_shard_stride, _u64p(data_len) if data_len is not None else None, parity_ptr,
+            parity_obj_stride, parity_shard_stride, first_bad_ptr))
+
+    def verify_batch_device(self, objs: Sequence[tuple], data_ptrs, parity_ptrs, first_bad_ptr, data_len=None,
+                            dev=0, stream=None):
+        """mxec_verify_batch_device: objects of mixed (k, m, shard_size), one
+        launch per m; first_bad_ptr is a device array of sum(m) uint64."""
+        arr = objs if isinstance(objs, ctypes.Array) else (N.Object * len(objs))(*[N.Object(k, m, s) for (k, m, s) in objs])
+        dp = data_ptrs if isinstance(data_ptrs, ctypes.Array) else _pp(data_ptrs)
+        pp = parity_ptrs if isinstance(parity_ptrs, ctypes.Array) else _pp(parity_ptrs)
+        dl = None if data_len is None else (data_len if isinstance(data_len, ctypes.Array) else _u64p(data_len))
+        _check(self._lib.mxec_verify_batch_device(self._h, dev, stream, arr, len(objs), dp, dl, pp, first_bad_ptr))
 
     def encode_batch_host(self, objs: Sequence[tuple], data_ptrs, parity_ptrs, data_len=None,
                           digests: Optional[np.ndarray] = None, return_rc: bool = False):
@@ -712,6 +755,20 @@ class Context:
         _check(self._lib.mxec_frame_aads(self._h, _ptr(p), p.size, first_index, n, out.ctypes.data))
         return [out[i].tobytes() for i in range(n)]
 
+    def scrub_object(self, ec_dir: str, parity: bool = True, digests: bool = False, heal: bool = False) -> dict:
+        """mxec_scrub_object over one `{key}.ec` directory.  parity: the GPU
+        parity check (cheap, cannot name the shard at fault); digests: SHA-256
+        of every shard against the manifest; heal: rebuild and rewrite damaged
+        shards (implies digests).  Returns the report as a dict; shard_state
+        has k + m entries (SHARD_*, SHARD_HEALED or-ed in)."""
+        flags = (SCRUB_PARITY if parity else 0) | (SCRUB_DIGESTS if digests else 0) | (SCRUB_HEAL if heal else 0)
+        r = N.ScrubReport()
+        _check(self._lib.mxec_scrub_object(self._h, ec_dir.encode(), flags, ctypes.byref(r)))
+        return {"k": int(r.k), "m": int(r.m), "verdict": int(r.verdict), "n_damaged": int(r.n_damaged),
+                "n_healed": int(r.n_healed), "parity_consistent": int(r.parity_consistent),
+                "parity_first_bad": int(r.parity_first_bad),
+                "shard_state": [int(x) for x in r.shard_state[: r.k + r.m]]}
+
     def try_reconstruct_data_chunk(self, ec_dir: str, target: int, capacity: int = 1 << 26) -> bytes:
         out = np.zeros(max(1, capacity), np.uint8)
         n = ctypes.c_uint64(0)
@@ -839,9 +896,11 @@ class ReedSolomon:
                 target[:] = parity[i].tobytes()
 
     def verify(self, shards: list) -> bool:
+        """The crate's verify: recomputed and compared on the GPU
+        (Context.verify); no parity comes back to the host."""
         size = self._check_shards(shards)
-        parity, _ = self.ctx.encode(shards[: self.k], self.m, size, digests=False)
-        return all(bytes(_u8(shards[self.k + i])) == parity[i].tobytes() for i in range(self.m))
+        ok, _ = self.ctx.verify(shards[: self.k], shards[self.k:], size)
+        return ok
 
     def _reconstruct(self, shards: list, data_only: bool) -> None:
         size = self._check_shards(shards, allow_none=True)

@@ -91,6 +91,37 @@ pub struct MxecMultipartPart {
     pub encrypted: u8,
 }
 
+/// `mxec_scrub_report`: what `mxec_scrub_object` found (its `out` argument).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct MxecScrubReport {
+    pub k: u32,
+    pub m: u32,
+    pub verdict: u32,
+    pub n_damaged: u32,
+    pub n_healed: u32,
+    pub parity_consistent: i32,
+    pub parity_first_bad: u64,
+    pub shard_state: [u8; 256],
+}
+
+/// `MXEC_VERIFY_OK`: a parity row that matches.
+pub const MXEC_VERIFY_OK: u64 = u64::MAX;
+
+// ---- mxec_scrub_object flags, verdicts and shard states ---------------------
+pub const MXEC_SCRUB_PARITY: u32 = 1;
+pub const MXEC_SCRUB_DIGESTS: u32 = 2;
+pub const MXEC_SCRUB_HEAL: u32 = 4;
+pub const MXEC_SCRUB_CLEAN: u32 = 0;
+pub const MXEC_SCRUB_DAMAGED: u32 = 1;
+pub const MXEC_SCRUB_HEALED: u32 = 2;
+pub const MXEC_SCRUB_UNRECOVERABLE: u32 = 3;
+pub const MXEC_SHARD_OK: u8 = 0;
+pub const MXEC_SHARD_MISSING: u8 = 1;
+pub const MXEC_SHARD_BAD_SIZE: u8 = 2;
+pub const MXEC_SHARD_BAD_DIGEST: u8 = 3;
+pub const MXEC_SHARD_HEALED: u8 = 0x80;
+
 // ---- mxec_ctx_pipe_stats counter indices ----------------------------------
 pub const MXEC_PIPE_STAT_COPIES_1D: c_int = 0;
 pub const MXEC_PIPE_STAT_COPIES_2D: c_int = 1;
@@ -185,6 +216,9 @@ extern "C" {
     pub fn mxec_get_object_chunked_async(ctx: *mut MxecCtx, ec_dir: *const c_char, offset: u64, length: u64, out: *mut u8, out_cap: u64, out_len: *mut u64, ticket: *mut *mut MxecTicket) -> c_int;
     pub fn mxec_encode_strided_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, k: c_int, m: c_int, shard_size: u64, n_obj: u64, data: *const u8, data_obj_stride: u64, data_shard_stride: u64, data_len: *const u64, parity: *mut u8, parity_obj_stride: u64, parity_shard_stride: u64, digests_dev: *mut u8) -> c_int;
     pub fn mxec_encode_batch_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, objs: *const MxecObject, n_obj: u64, data: *const *const u8, data_len: *const u64, parity: *const *mut u8, digests_dev: *mut u8) -> c_int;
+    pub fn mxec_verify(ctx: *mut MxecCtx, k: c_int, m: c_int, shard_size: usize, data: *const *const u8, data_len: *const usize, parity: *const *const u8, first_bad: *mut u64, consistent: *mut c_int) -> c_int;
+    pub fn mxec_verify_strided_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, k: c_int, m: c_int, shard_size: u64, n_obj: u64, data: *const u8, data_obj_stride: u64, data_shard_stride: u64, data_len: *const u64, parity: *const u8, parity_obj_stride: u64, parity_shard_stride: u64, first_bad_dev: *mut u64) -> c_int;
+    pub fn mxec_verify_batch_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, objs: *const MxecObject, n_obj: u64, data: *const *const u8, data_len: *const u64, parity: *const *const u8, first_bad_dev: *mut u64) -> c_int;
     pub fn mxec_encode_batch_host(ctx: *mut MxecCtx, objs: *const MxecObject, n_obj: u64, data: *const *const u8, data_len: *const u64, parity: *const *mut u8, digests: *mut [u8; 32], status_out: *mut i32) -> c_int;
     pub fn mxec_reconstruct_batch_host(ctx: *mut MxecCtx, objs: *const MxecObject, n_obj: u64, shards: *const *mut u8, shard_len: *const u64, present: *mut u8, expected_sha256: *const [u8; 32], flags: u32, status_out: *mut i32) -> c_int;
     pub fn mxec_reconstruct_strided_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, k: c_int, m: c_int, shard_size: u64, n_obj: u64, shards: *mut u8, obj_stride: u64, shard_stride: u64, shard_len: *const u64, present: *mut u8, expected_sha_dev: *const u8, flags: u32, status_out: *mut i32) -> c_int;
@@ -212,6 +246,8 @@ extern "C" {
     pub fn mxec_reader_open(ctx: *mut MxecCtx, ec_dir: *const c_char, offset: u64, length: u64, batch_bytes: u64, out: *mut *mut MxecReader) -> c_int;
     pub fn mxec_reader_read(r: *mut MxecReader, buf: *mut u8, cap: u64) -> i64;
     pub fn mxec_reader_close(r: *mut MxecReader);
+    /// `out`: a `*mut MxecScrubReport`.
+    pub fn mxec_scrub_object(ctx: *mut MxecCtx, ec_dir: *const c_char, flags: u32, out: *mut c_void) -> c_int;
     pub fn mxec_try_reconstruct_data_chunk(ctx: *mut MxecCtx, ec_dir: *const c_char, target: u32, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
 }
 
