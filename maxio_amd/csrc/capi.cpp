@@ -26,7 +26,7 @@ namespace {
 // MXEC_PIPE_COPY (knobs.hpp): whether a host-pointer call's copies of
 // mxec_host_alloc memory may go by CU-wave copy kernels -- the reconstruct /
 // hash (GET) paths under auto and waves, the encode (PUT) path under waves
-// only (pipeline.cpp has the measurements behind the split).
+// only (copy_watch.hpp has the measurements behind the split).
 bool copy_waves_get(const Device& d) {
     if (!d.kn) return false;
     if (d.kn->pipe_copy == 1) return true;

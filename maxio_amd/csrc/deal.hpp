@@ -1,5 +1,5 @@
 // deal.hpp — which device of a context gets each object of a host batch
-// (pipeline.cpp mxec_encode_batch_host).  No HIP dependency, so the dealing
+// (pipeline.hpp deal_batch).  No HIP dependency, so the dealing
 // is unit-tested on the CPU (tests/c_manifest/deal_check.cpp).
 #pragma once
 #include <algorithm>

@@ -27,7 +27,7 @@ struct Knobs {
     int sha_form = 0;              // MXEC_SHA_FORM: 0 auto, 1 one, 2 split, 3 stream, 6 lagpair
     int desc_upload = 1;           // MXEC_DESC_UPLOAD: 0 inline, 1 auto, 2 side stream
     uint64_t pipe_piece = uint64_t(1) << 20;  // MXEC_PIPE_PIECE_MB (0: whole chunks)
-    bool pipe_piece_auto = true;   // MXEC_PIPE_PIECE_MB unset: 1, 2 or 4 MiB per wave (pipeline.cpp)
+    bool pipe_piece_auto = true;   // MXEC_PIPE_PIECE_MB unset: 1, 2 or 4 MiB per wave (pipeline.hpp)
     int pipe_copy = 2;             // MXEC_PIPE_COPY: 0 sdma (hipMemcpyAsync); 1 waves (copy_kernel.hip
                                    //   for every host batch); 2 auto: SDMA, its upload rate timed as
                                    //   it goes; waves after it runs below pipe_sdma_floor
@@ -35,7 +35,7 @@ struct Knobs {
     uint64_t get_window = uint64_t(1) << 30;  // MXEC_GET_WINDOW: bytes of chunks per GET window
     int get_vgroups = 0;           // MXEC_GET_VGROUPS: verification groups of a verified host GET wave (1..8; 0 = per wave)
     bool get_speculate = true;     // MXEC_GET_SPECULATE: the verified host GET rebuilds each piece as it
-                                   //   arrives, before the verdict (pipeline.cpp spec_piece)
+                                   //   arrives, before the verdict (pipeline_get.cpp spec_piece)
     int pipe_lanes = 4;            // MXEC_PIPE_LANES: host-batch calls admitted at once per device (1..8)
     long gather_us = 100;          // MXEC_GATHER_US
     long gather_max_us = 2000;     // MXEC_GATHER_MAX_US

@@ -33,7 +33,7 @@ struct RsObject {
 
 // Applies each object's matrix; all objects share (k, r, shard_size).
 // arena: take the descriptor tables from it instead of the slot's ring (many
-// launches in flight, see pipeline.cpp).
+// launches in flight, see pipeline.hpp).
 // tune = false: the default grid, and the grid tuner neither picks nor
 // records (the batch allocator's placement probes, placement.cpp).
 int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, int r,
@@ -181,7 +181,7 @@ struct DevScope {
 int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const uint8_t*>& ptrs,
                   const std::vector<uint64_t>& lens, uint32_t which, uint8_t* out_dev, uint64_t stride);
 
-// Creates the device's host-pipeline hub and its streams (pipeline.cpp),
+// Creates the device's host-pipeline hub and its streams (pipe_hub.cpp),
 // called by mxec_open for every device.
 int pipe_open(Device& dev);
 

@@ -1,5 +1,5 @@
 // piece_grid.hpp -- the piece grid of the host pipeline's piece-major waves
-// (pipeline.cpp wave_pieces / verify_enqueue).  Header-only and free of HIP
+// (pipeline_put.cpp wave_pieces / pipeline_get.cpp verify_enqueue).  Header-only and free of HIP
 // so tests/c_manifest/piece_grid_check.cpp can test it on the CPU.
 //
 // A wave moves every chunk in pieces: a ramp of pieces doubling from `ramp`

@@ -186,7 +186,7 @@ bool pinned_mapped(const void* p, uint64_t len) {
 
 namespace {
 // The segments as CU-wave copy blocks, the table read in place from the
-// slot's descriptor ring (copy_kernel.hip; 16 workgroups, as pipeline.cpp).
+// slot's descriptor ring (copy_kernel.hip; 16 workgroups, as host_copy.hpp).
 int wave_copy_segments(Slot& slot, hipStream_t s, const std::vector<CopyBlk>& blks, bool to_host) {
     if (blks.empty()) return MXEC_OK;
     DescWriter w(slot);

@@ -148,7 +148,7 @@ constexpr uint64_t kStagePiece = uint64_t(8) << 20;
 // dst_off and not overlap.
 // waves: segments wholly inside mxec_host_alloc memory may move by a CU-wave
 // copy kernel (copy_kernel.hip) instead of SDMA (the host reconstruct and
-// hash paths, MXEC_PIPE_COPY auto / waves; pipeline.cpp has the measurements).
+// hash paths, MXEC_PIPE_COPY auto / waves; copy_watch.hpp has the measurements).
 int upload_segments(Slot& slot, hipStream_t s, uint8_t* dev_base, const std::vector<UploadSeg>& segs,
                     bool waves = false);
 // One device -> host download segment: len bytes from src_off to dst.
@@ -211,7 +211,7 @@ struct Device {
     // alternate between pretend nodes 0 and 1), and whether the context's
     // devices sit on more than one node: only then does the host pipeline
     // deal objects by where their pages are and keep its page-locked rings
-    // on the device's node (pipeline.cpp).
+    // on the device's node (pipeline.hpp, pipe_hub.cpp).
     int numa_node = -1;
     bool ctx_multi_node = false;
     const Knobs* kn = nullptr;  // the context's settings (read at mxec_open)
@@ -285,7 +285,7 @@ struct Device {
         uint64_t seq;  // the table's upload (Device::CoefEntry)
     };
     std::unordered_map<PatternKey, PatternVal, PatternHash> patterns;
-    // Host-batch pipeline state (pipeline.cpp PipeHub): the four shared
+    // Host-batch pipeline state (pipe_hub.hpp PipeHub): the four shared
     // streams and the per-call lanes (pinned rings, pools, descriptor
     // arenas); created on first use and kept.  Up to MXEC_PIPE_LANES calls
     // run at once per device, their waves interleaving on the same streams.
@@ -301,7 +301,7 @@ struct Device {
     std::atomic<uint64_t> sdma_probes{0}, sdma_slow_verdicts{0}, sdma_last_mbps{0};
     std::atomic<uint64_t> sdma_down_probes{0}, sdma_down_slow_verdicts{0}, sdma_down_last_mbps{0};
     // Piece-major verified reconstruct waves and the verification groups
-    // they ran as (pipeline.cpp verify_cuts).
+    // they ran as (pipeline_get.cpp verify_cuts).
     std::atomic<uint64_t> verify_waves{0}, verify_groups{0};
     // The watch's verdicts as holds (steady_clock ns): calls that start
     // before these instants copy mxec_host_alloc memory by waves, uploads /
@@ -310,14 +310,14 @@ struct Device {
     // (capi.cpp copy_waves_get).
     std::atomic<int64_t> waves_up_until_ns{0}, waves_down_until_ns{0};
     // Until this instant a lone speculating verified GET wave downloads by
-    // waves (pipeline.cpp spec_judge).
+    // waves (copy_watch.hpp spec_judge).
     std::atomic<int64_t> spec_waves_until_ns{0};
     std::atomic<int> spec_slow_run{0};  // slow verdicts in a row
-    std::atomic<int> down_slow_run{0};  // slow SDMA download brackets in a row (pipeline watch_judge)
+    std::atomic<int> down_slow_run{0};  // slow SDMA download brackets in a row (copy_watch.hpp judge)
     // Host-batch calls (per device share), those admitted while another ran
     // on the device, speculative piece rebuilds of verified GETs and the
     // objects re-decoded after a verdict, and host waits that paced a shared
-    // call's enqueue (pipeline.cpp).
+    // call's enqueue (host_copy.cpp pace).
     std::atomic<uint64_t> pipe_calls{0}, pipe_calls_shared{0}, spec_pieces{0}, spec_redos{0}, pace_waits{0};
     // SHA-256 combiner (combiner.cpp): one launch for the verification work
     // of every concurrent caller on this device.

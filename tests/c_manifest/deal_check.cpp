@@ -1,5 +1,5 @@
 // CPU unit test of the host-batch dealing (maxio_amd/csrc/deal.hpp, used by
-// pipeline.cpp mxec_encode_batch_host): a uniform batch keeps o mod D; a
+// pipeline.hpp deal_batch): a uniform batch keeps o mod D; a
 // mixed 64 KiB..10 MiB batch over 8 devices lands within 10 % bytes.
 #include <cstdio>
 #include <random>

@@ -2,7 +2,7 @@
 
 MaxIO serves PUTs (filesystem.rs:686-828) and GETs (chunk_reader.rs:87-226)
 at once on a multi-thread tokio runtime (main.rs:81); the library admits up
-to MXEC_PIPE_LANES host-batch calls per device at once (pipeline.cpp
+to MXEC_PIPE_LANES host-batch calls per device at once (pipe_hub.hpp
 PipeHub), their waves interleaving on the device's four pipeline streams.
 
 * A PUT with digests and a verified GET from two threads, started together

@@ -1,5 +1,5 @@
 """GPU: the verified host GET, as one verification group, as the count the
-library picks per wave (the default) and as pipelined groups (MXEC_GET_VGROUPS; pipeline.cpp verify_cuts / verify_enqueue
+library picks per wave (the default) and as pipelined groups (MXEC_GET_VGROUPS; pipeline_get.cpp verify_cuts / verify_enqueue
 / verify_collect): group j + 1's pieces go up and hash while the host
 collects group j's verdicts, rebuilds it and sends its shards down.  Reference: try_reconstruct_data_chunk,
 chunk_reader.rs:157-226, per object.
@@ -28,7 +28,7 @@ TOO_FEW_SHARDS_PRESENT = -10  # include/maxio_ec.h MXEC_E_TOO_FEW_SHARDS_PRESENT
 
 @pytest.mark.parametrize("groups", [0, 1, 3])
 def test_verified_get_in_groups_matches_originals(ctx_with, groups):
-    """groups 0: the per-wave choice (pipeline.cpp verify_cuts), which keeps
+    """groups 0: the per-wave choice (pipeline_get.cpp verify_cuts), which keeps
     this batch -- a 34 ms upload against a 19 ms chain -- as one group."""
     ctx = ctx_with(MXEC_GET_VGROUPS=str(groups))
     k, m, n = 8, 4, 160

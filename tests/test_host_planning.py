@@ -8,7 +8,9 @@
   10 % per device at 2/4/8 devices) and a uniform one as object o -> o mod D
   (VERDICT r2 item 6);
 * the piece grid of the piece-major host waves tiles every message with
-  and without a ramp and after widening mid-wave (piece_grid.hpp)."""
+  and without a ramp and after widening mid-wave (piece_grid.hpp);
+* the wave cutter of the host batch calls keeps every object in exactly one
+  wave, in order, within the pool allowance unless alone (wave_cut.hpp)."""
 from __future__ import annotations
 
 import os
@@ -23,7 +25,7 @@ HERE = os.path.join(ROOT, "tests", "c_manifest")
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 @pytest.mark.parametrize("src,ok", [("sha_guard_check.cpp", "sha guard ok"), ("deal_check.cpp", "deal ok"),
-                                    ("piece_grid_check.cpp", "piece grid ok")])
+                                    ("piece_grid_check.cpp", "piece grid ok"), ("wave_cut_check.cpp", "wave cut ok")])
 def test_host_planning(tmp_path, src, ok):
     exe = str(tmp_path / src.split(".")[0])
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",

@@ -3,7 +3,7 @@ box by opening device 0 as two logical devices (mxec_open_test logical_devices=2
 with its own slots, streams, coefficient arena, combiner and pipeline):
 
 * mxec_encode_batch_host deals objects to per-device workers (o mod D,
-  pipeline.cpp) — odd object counts, mixed (k, m, S), short last chunks and a
+  pipeline.hpp) — odd object counts, mixed (k, m, S), short last chunks and a
   failing object, bit-exact against the oracle, errors aggregated;
 * host-API calls round-robin over the devices (ops.hpp DevScope / pick_device)
   from many threads at once;

@@ -5,7 +5,7 @@ digests, filesystem.rs:1107-1135; the GET's rebuild, chunk_reader.rs:157-226).
 * PUT with digests in 2 / 4 MiB pieces (MXEC_PIPE_PIECE_MB, product knob) and
   with the piece size chosen per wave at a batch large enough to be
   upload-bound: the same piece of an object's k data chunks goes up as one
-  2D SDMA copy (pipeline.cpp flush_up), its m parity pieces come down as
+  2D SDMA copy (host_copy.hpp flush_up), its m parity pieces come down as
   one (flush_down).  mxec_ctx_pipe_stats proves the 2D copies ran.  Shards
   off the piece grid; a short and an empty last data chunk break the 2D run
   in the middle of the batch.  EVERY object's parity and all k+m digests
@@ -198,7 +198,7 @@ def test_get_download_watch(floor):
     device's downloads go by waves for the next 1 s (the third GET).  A
     lone verified GET speculates: its downloads go by SDMA unless a hold is
     on, the wave judged once after the fact from how long its downloads ran
-    past the last verdict (pipeline.cpp spec_judge), its uploads by waves.
+    past the last verdict (copy_watch.hpp spec_judge), its uploads by waves.
     16 x 4+2 objects of
     4 MiB + 4 KiB shards, two data shards erased in each: every rebuilt shard
     equals the original every time."""

@@ -6,7 +6,7 @@ GETs back to back ("fresh"), then `reps` GETs each right after torch
 allocates, fills and frees `--churn-gb` GB of HBM ("churn").  Rounds
 interleaved; the parent never touches the GPU.
 
-  python tools/get_churn_ab.py --settings "sdma:;waves:MXEC_SPEC_DOWN_WAVES=1" --lab
+  python tools/get_churn_ab.py --settings "auto:;waves:MXEC_PIPE_COPY=waves"
 """
 from __future__ import annotations
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timelines of host batch calls (lab build: MXEC_PIPE_TRACE=1, pipeline.cpp
+"""Timelines of host batch calls (lab build: MXEC_PIPE_TRACE=1, pipe_trace.hpp
 PipeTrace -- one stderr JSON line per wave, GPU marks and host marks against
 one process-wide reference, so concurrent calls line up): a PUT with digests
 alone, a verified GET alone, and the two started together, 128 x 4+2 x 10 MiB

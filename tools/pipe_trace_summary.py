@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Summarise tools/pipe_trace.py's stderr (MXEC_PIPE_TRACE wave lines,
-pipeline.cpp PipeTrace): per phase and wave, the GPU marks by kind (first /
+pipe_trace.hpp PipeTrace): per phase and wave, the GPU marks by kind (first /
 last time, count) and the host marks, all in ms against one reference.
 
   python tools/pipe_trace_summary.py gpurun_out/r6d/trace_auto.err

@@ -5,7 +5,7 @@ after the device-resident configs[1] batch was freed), every timed call
 listed: each setting in a fresh child process (--child), rounds interleaved.
 The parent never touches the GPU.
 
-  python tools/spec_grid_ab.py --settings "cap:;nocap:MXEC_SPEC_BLOCKS=0" --rounds 2 --reps 8 --lab
+  python tools/spec_grid_ab.py --settings "spec:;nospec:MXEC_GET_SPECULATE=0" --rounds 2 --reps 8
 """
 from __future__ import annotations
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Which copy engine should the host batch calls use?  The SDMA watch
-(pipeline.cpp watch_open / watch_judge) against the same batches with every
+(copy_watch.hpp CopyWatch) against the same batches with every
 copy forced to SDMA and to CU waves.
 
 Per batch size (`--objects`, 4+2 x 10 MiB from mxec_host_alloc memory, two
@@ -75,23 +75,13 @@ def main() -> int:
         dig2 = np.zeros_like(dig)
         for kind in a.kinds.split(","):
             for mode in a.modes.split(","):
-                # sdma_down_waves (lab build): uploads by SDMA, downloads by
-                # waves; auto_nowatch: auto with the watch off (floor 0)
-                # *_cus16 (lab): copy streams on 16 CUs, compute streams on the rest
-                env = {"sdma_down_waves": {"MXEC_PIPE_COPY": "sdma"},
-                       "sdma_down_waves_cus16": {"MXEC_PIPE_COPY": "auto", "MXEC_PIPE_SDMA_FLOOR": "0",
-                                                 "MXEC_PIPE_COPY_CUS": "16"},
-                       "waves_cus16": {"MXEC_PIPE_COPY": "waves", "MXEC_PIPE_COPY_CUS": "16"},
-                       "auto_nowatch": {"MXEC_PIPE_COPY": "auto", "MXEC_PIPE_SDMA_FLOOR": "0"}}.get(
-                           mode, {"MXEC_PIPE_COPY": mode})
+                # auto_nowatch: auto with the watch off (floor 0)
+                env = {"auto_nowatch": {"MXEC_PIPE_COPY": "auto", "MXEC_PIPE_SDMA_FLOOR": "0"}}.get(
+                    mode, {"MXEC_PIPE_COPY": mode})
                 os.environ.update(env)
                 ctx = maxio_amd.Context(streams_per_device=2)
                 for key in env:
                     os.environ.pop(key)
-                if mode.startswith("sdma_down_waves"):
-                    os.environ["MXEC_PIPE_DOWN_WAVES"] = "1"
-                else:
-                    os.environ.pop("MXEC_PIPE_DOWN_WAVES", None)
                 row = {"objects": n, "kind": kind, "mode": mode, "churn_GB": a.churn, "calls": []}
                 for rep in range(a.reps + 1):
                     if rep == 1 and a.churn_each > 0:  # after the warm call, right before the timed ones
