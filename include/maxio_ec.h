@@ -350,6 +350,57 @@ int mxec_verify_batch_device(mxec_ctx* ctx, int dev, void* stream,
                              const uint8_t* const* parity,
                              uint64_t* first_bad_dev);
 
+/* ---- locate: which shard is damaged, from the parity alone -----------------
+ * The verify's walk, but on a mismatch every bad byte column (one whose m
+ * syndrome bytes s_i = stored_parity_i ^ recomputed_parity_i are not all
+ * zero) is classified.  Exactly one s_i non-zero: parity shard k + i.  All m
+ * non-zero and s = M[:, j] * e for one data shard j whose length reaches the
+ * column: data shard j.  Anything else fits no single shard:
+ * MXEC_LOCATE_NO_SHARD.  The encoding matrix is MDS, so a corruption confined
+ * to one shard is named uniquely, column by column.  Needs 2 <= m <= 8: one
+ * parity row cannot tell shards apart, more than eight do not fit the
+ * kernel's one row block (MXEC_E_INVALID_ARG; m == 0 is
+ * MXEC_E_TOO_FEW_PARITY_SHARDS); every other error is the verify's, and
+ * all are decided before anything is enqueued.  A clean stripe costs what
+ * the verify costs and writes nothing. */
+#define MXEC_LOCATE_NO_SHARD 0xFFFFFFFEu
+struct mxec_locate_result {
+    uint64_t first_bad; /* lowest bad byte column, MXEC_VERIFY_OK if none */
+    uint64_t n_bad;     /* number of bad byte columns */
+    uint32_t shard_min; /* min / max over the bad columns' candidates (shard */
+    uint32_t shard_max; /*   index or MXEC_LOCATE_NO_SHARD); clean: UINT32_MAX / 0 */
+};
+typedef struct mxec_locate_result mxec_locate_result;
+/* What a result amounts to (pure host function, no context):
+ * MXEC_LOCATE_CLEAN (n_bad == 0), _ONE (shard_min == shard_max < 256;
+ * *shard, if not NULL, receives it), _MANY (everything else).  `result`
+ * points at a mxec_locate_result. */
+#define MXEC_LOCATE_CLEAN 0
+#define MXEC_LOCATE_ONE 1
+#define MXEC_LOCATE_MANY 2
+int mxec_locate_outcome(const void* result, uint32_t* shard);
+/* One object in host memory, through the host verify's one-request path: the
+ * shards go up, 24 bytes come back.  `out` points at a mxec_locate_result. */
+int mxec_locate(mxec_ctx* ctx, int k, int m, size_t shard_size,
+                const uint8_t* const* data, const size_t* data_len,
+                const uint8_t* const* parity, void* out);
+/* Device-resident batches, laid out and enqueued as the verify's.  out_dev is
+ * a device array of n_obj mxec_locate_result records, initialised on `stream`
+ * ahead of the kernel and filled by it: read it after the stream has
+ * drained.  Objects of a batch that share m share one launch. */
+int mxec_locate_strided_device(mxec_ctx* ctx, int dev, void* stream, int k,
+                               int m, uint64_t shard_size, uint64_t n_obj,
+                               const uint8_t* data, uint64_t data_obj_stride,
+                               uint64_t data_shard_stride,
+                               const uint64_t* data_len, const uint8_t* parity,
+                               uint64_t parity_obj_stride,
+                               uint64_t parity_shard_stride, void* out_dev);
+int mxec_locate_batch_device(mxec_ctx* ctx, int dev, void* stream,
+                             const mxec_object* objs, uint64_t n_obj,
+                             const uint8_t* const* data,
+                             const uint64_t* data_len,
+                             const uint8_t* const* parity, void* out_dev);
+
 /* End-to-end PUT compute for many objects whose chunks are in HOST memory
  * (request bodies) — the batched form of mxec_encode.  Same array layout as
  * mxec_encode_batch_device but host pointers; digests (host, sum(k+m)) and
@@ -716,6 +767,32 @@ struct mxec_scrub_report {
 };
 typedef struct mxec_scrub_report mxec_scrub_report;
 int mxec_scrub_object(mxec_ctx* ctx, const char* ec_dir, uint32_t flags, void* out);
+
+/* ---- locate / fast heal of one EC object ----------------------------------
+ * The scrub's cheap pass, naming the shard: reads the manifest and sizes
+ * every shard file exactly as mxec_scrub_object does, then runs mxec_locate
+ * over them -- no SHA-256 of any present shard.
+ *   outcome MXEC_LOCATE_CLEAN, _ONE (`shard` is the damaged one), _MANY, or
+ *           _SKIPPED: no parity location is possible (m < 2, m > 8, or a
+ *           shard file missing / wrong-sized) -- run mxec_scrub_object.
+ *   flags   MXEC_LOCATE_F_HEAL  on outcome ONE, that shard alone is rebuilt
+ *           from the others, the rebuilt shard alone is hashed against the
+ *           manifest's digest, and on equality written like a scrub's heal
+ *           (temporary name, fsync, rename): healed = 1.  On disagreement,
+ *           or a digest that does not parse, nothing is created, changed or
+ *           removed and healed = 0: fall back to the scrub's HEAL.
+ * Returns MXEC_OK whenever the pass ran; manifest, I/O and RS-init errors as
+ * from mxec_scrub_object; unknown flags MXEC_E_INVALID_ARG.  `out` points at
+ * a mxec_locate_report. */
+#define MXEC_LOCATE_SKIPPED 3
+#define MXEC_LOCATE_F_HEAL 1u
+struct mxec_locate_report {
+    uint32_t k, m, outcome, shard; /* shard valid when outcome == MXEC_LOCATE_ONE */
+    uint64_t first_bad, n_bad;
+    uint32_t healed, reserved; /* healed: 1 iff the shard file was replaced */
+};
+typedef struct mxec_locate_report mxec_locate_report;
+int mxec_locate_object(mxec_ctx* ctx, const char* ec_dir, uint32_t flags, void* out);
 
 #ifdef __cplusplus
 }

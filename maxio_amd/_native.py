@@ -90,6 +90,32 @@ class ScrubReport(ctypes.Structure):
     ]
 
 
+class LocateResult(ctypes.Structure):
+    """mxec_locate_result: one object's record of a locate launch."""
+
+    _fields_ = [
+        ("first_bad", ctypes.c_uint64),
+        ("n_bad", ctypes.c_uint64),
+        ("shard_min", ctypes.c_uint32),
+        ("shard_max", ctypes.c_uint32),
+    ]
+
+
+class LocateReport(ctypes.Structure):
+    """mxec_locate_report: what mxec_locate_object found (and healed)."""
+
+    _fields_ = [
+        ("k", ctypes.c_uint32),
+        ("m", ctypes.c_uint32),
+        ("outcome", ctypes.c_uint32),
+        ("shard", ctypes.c_uint32),
+        ("first_bad", ctypes.c_uint64),
+        ("n_bad", ctypes.c_uint64),
+        ("healed", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 class Object(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("m", ctypes.c_int32), ("shard_size", ctypes.c_uint64)]
 
@@ -136,6 +162,12 @@ _SIGS = {
         INT, [P, INT, P, INT, INT, U64, U64, P, U64, U64, U64P, P, U64, U64, P]),
     "mxec_verify_batch_device": (INT, [P, INT, P, ctypes.POINTER(Object), U64, PP, U64P, PP, P]),
     "mxec_scrub_object": (INT, [P, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(ScrubReport)]),
+    "mxec_locate_outcome": (INT, [ctypes.POINTER(LocateResult), ctypes.POINTER(ctypes.c_uint32)]),
+    "mxec_locate": (INT, [P, INT, INT, SZ, PP, SZP, PP, ctypes.POINTER(LocateResult)]),
+    "mxec_locate_strided_device": (
+        INT, [P, INT, P, INT, INT, U64, U64, P, U64, U64, U64P, P, U64, U64, P]),
+    "mxec_locate_batch_device": (INT, [P, INT, P, ctypes.POINTER(Object), U64, PP, U64P, PP, P]),
+    "mxec_locate_object": (INT, [P, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(LocateReport)]),
     "mxec_encode_batch_host": (INT, [P, ctypes.POINTER(Object), U64, PP, U64P, PP, U8P, I32P]),
     "mxec_reconstruct_batch_host": (INT, [P, ctypes.POINTER(Object), U64, PP, U64P, U8P, U8P, ctypes.c_uint32, I32P]),
     "mxec_reconstruct_strided_device": (

@@ -17,6 +17,8 @@
 #include <unistd.h>
 
 #include "../../include/maxio_ec.h"
+#include "kernels.hpp"
+#include "locate_plan.hpp"
 #include "ops.hpp"
 
 using namespace mxec;
@@ -854,6 +856,182 @@ int mxec_verify_batch_device(mxec_ctx* ctx, int dev, void* stream, const mxec_ob
             return MXEC_OK;
         }, [&]() -> int {
             MXEC_HIP(hipMemsetAsync(first_bad_dev, 0xFF, size_t(8 * psum), s));
+            return run_rs_mixed(*ds.d, *ds.slot, s, groups);
+        });
+    });
+}
+
+// ---- locate ------------------------------------------------------------------
+
+static_assert(sizeof(mxec_locate_result) == 24 && sizeof(LocateRec) == sizeof(mxec_locate_result) &&
+                  offsetof(LocateRec, n_bad) == offsetof(mxec_locate_result, n_bad) &&
+                  offsetof(LocateRec, shard_min) == offsetof(mxec_locate_result, shard_min) &&
+                  offsetof(LocateRec, shard_max) == offsetof(mxec_locate_result, shard_max),
+              "the kernel's record is the header's");
+static_assert(kLocateNoShard == MXEC_LOCATE_NO_SHARD, "one sentinel");
+
+namespace {
+// The verify's (k, m) checks, then the locate's own: one parity row cannot
+// tell shards apart, more than eight do not fit one row block.
+int check_km_locate(int k, int m) {
+    MXEC_TRY(check_km(k, m));
+    if (m < 2) return set_error(MXEC_E_INVALID_ARG, "locate needs at least two parity shards");
+    if (m > 8) return set_error(MXEC_E_INVALID_ARG, "locate takes at most eight parity shards");
+    return MXEC_OK;
+}
+}  // namespace
+
+int mxec_locate_outcome(const void* result, uint32_t* shard) {
+    if (!result) return MXEC_LOCATE_MANY;
+    return locate_outcome(static_cast<const mxec_locate_result*>(result), shard);
+}
+
+int mxec_locate(mxec_ctx* ctx, int k, int m, size_t shard_size, const uint8_t* const* data,
+                const size_t* data_len, const uint8_t* const* parity, void* out) {
+    return guarded([&] {
+        MXEC_TRY(check_km_locate(k, m));
+        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
+        if (!data || !parity || !out) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        std::vector<uint64_t> len(static_cast<size_t>(k + m), shard_size);
+        for (int j = 0; j < k; ++j) {
+            len[size_t(j)] = data_len ? data_len[j] : shard_size;
+            if (len[size_t(j)] > shard_size)
+                return set_error(MXEC_E_INCORRECT_SHARD_SIZE, "data chunk longer than shard_size");
+            if (len[size_t(j)] && !data[j]) return set_error(MXEC_E_INVALID_ARG, "null data chunk");
+        }
+        for (int i = 0; i < m; ++i)
+            if (!parity[i]) return set_error(MXEC_E_INVALID_ARG, "null parity shard");
+        DevScope ds;
+        MXEC_TRY(ds.open(ctx, -1));
+        Slot& slot = *ds.slot;
+        hipStream_t s = slot.stream;
+        // The shards as mxec_verify stages them, then the one record.
+        const uint64_t sa = round_up(shard_size, kSlotAlign);
+        const uint64_t rec_off = sa * uint64_t(k + m);
+        MXEC_TRY(slot.shards.ensure(rec_off + sizeof(LocateRec)));
+        auto* base = static_cast<uint8_t*>(slot.shards.p);
+        auto* rec = reinterpret_cast<LocateRec*>(base + rec_off);
+        std::vector<const uint8_t*> in(static_cast<size_t>(k));
+        std::vector<uint8_t*> stored(static_cast<size_t>(m));
+        std::vector<UploadSeg> up;
+        for (int j = 0; j < k; ++j) {
+            in[size_t(j)] = base + sa * uint64_t(j);
+            if (len[size_t(j)]) up.push_back({sa * uint64_t(j), data[j], len[size_t(j)]});
+        }
+        for (int i = 0; i < m; ++i) {
+            stored[size_t(i)] = base + sa * uint64_t(k + i);
+            up.push_back({sa * uint64_t(k + i), parity[i], shard_size});
+        }
+        MXEC_TRY(upload_segments(slot, s, base, up, copy_waves_get(*ds.d)));
+        uint32_t off = 0;
+        MXEC_TRY(with_stable_coef(
+            *ds.d, s, [&] { return encode_coef(*ds.d, k, m, &off); },
+            [&] {
+                MXEC_HIP(launch_locate_init(rec, 1, s));
+                RsObject ob{in.data(), len.data(), stored.data(), len.data() + k, off, nullptr, rec};
+                return run_rs(*ds.d, slot, s, shard_size, k, m, {ob});
+            }));
+        std::vector<DownloadSeg> down{{rec_off, static_cast<uint8_t*>(out), sizeof(LocateRec)}};
+        return download_segments(slot, s, base, down, false);
+    });
+}
+
+int mxec_locate_strided_device(mxec_ctx* ctx, int dev, void* stream, int k, int m, uint64_t shard_size,
+                               uint64_t n_obj, const uint8_t* data, uint64_t data_obj_stride,
+                               uint64_t data_shard_stride, const uint64_t* data_len, const uint8_t* parity,
+                               uint64_t parity_obj_stride, uint64_t parity_shard_stride, void* out_dev) {
+    return guarded([&] {
+        MXEC_TRY(check_km_locate(k, m));
+        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
+        if (n_obj == 0) return MXEC_OK;
+        if (!data || !parity) return set_error(MXEC_E_INVALID_ARG, "null base pointer");
+        if (!out_dev) return set_error(MXEC_E_INVALID_ARG, "null result array");
+        DevScope ds;
+        MXEC_TRY(ds.open(ctx, dev));
+        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
+        auto* recs = static_cast<LocateRec*>(out_dev);
+        uint32_t off = 0;
+        std::vector<uint64_t> len(static_cast<size_t>(k + m), shard_size);
+        for (int j = 0; j < k; ++j)
+            if (data_len) len[size_t(j)] = std::min<uint64_t>(data_len[j], shard_size);
+        std::vector<const uint8_t*> in(static_cast<size_t>(n_obj * k));
+        std::vector<uint8_t*> stored(static_cast<size_t>(n_obj * m));  // read only
+        std::vector<RsObject> objs(static_cast<size_t>(n_obj));
+        for (uint64_t o = 0; o < n_obj; ++o) {
+            for (int j = 0; j < k; ++j) in[o * k + j] = data + o * data_obj_stride + j * data_shard_stride;
+            for (int i = 0; i < m; ++i)
+                stored[o * m + i] = const_cast<uint8_t*>(parity) + o * parity_obj_stride + i * parity_shard_stride;
+            objs[o] = RsObject{&in[o * k], len.data(), &stored[o * m], len.data() + k, 0, nullptr, recs + o};
+        }
+        return with_stable_coef(
+            *ds.d, s, [&] { return encode_coef(*ds.d, k, m, &off); },
+            [&] {
+                // Initialised inside the launch step: a pass queued again
+                // after a table recycle (with_stable_coef) starts from clean
+                // records, so n_bad counts one pass.
+                MXEC_HIP(launch_locate_init(recs, n_obj, s));
+                for (auto& ob : objs) ob.coef_off = off;
+                return run_rs(*ds.d, *ds.slot, s, shard_size, k, m, objs);
+            });
+    });
+}
+
+int mxec_locate_batch_device(mxec_ctx* ctx, int dev, void* stream, const mxec_object* objs, uint64_t n_obj,
+                             const uint8_t* const* data, const uint64_t* data_len,
+                             const uint8_t* const* parity, void* out_dev) {
+    return guarded([&] {
+        if (n_obj == 0) return MXEC_OK;
+        if (!objs || !data || !parity || !out_dev) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        // Every object's (k, m) before a device is touched.
+        std::vector<uint64_t> dofs(static_cast<size_t>(n_obj)), pofs(static_cast<size_t>(n_obj));
+        uint64_t dsum = 0, psum = 0;
+        for (uint64_t o = 0; o < n_obj; ++o) {
+            MXEC_TRY(check_km_locate(objs[o].k, objs[o].m));
+            if (objs[o].shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
+            dofs[o] = dsum;
+            pofs[o] = psum;
+            dsum += uint64_t(objs[o].k);
+            psum += uint64_t(objs[o].m);
+        }
+        std::vector<uint8_t*> stored(static_cast<size_t>(psum));  // read only
+        for (uint64_t i = 0; i < psum; ++i) {
+            if (!parity[i]) return set_error(MXEC_E_INVALID_ARG, "null parity pointer " + std::to_string(i));
+            stored[i] = const_cast<uint8_t*>(parity[i]);
+        }
+        std::vector<uint64_t> dl(static_cast<size_t>(dsum)), pl(static_cast<size_t>(psum));
+        for (uint64_t o = 0; o < n_obj; ++o) {
+            for (int j = 0; j < objs[o].k; ++j) {
+                const uint64_t idx = dofs[o] + uint64_t(j);
+                dl[idx] = data_len ? std::min<uint64_t>(data_len[idx], objs[o].shard_size) : objs[o].shard_size;
+            }
+            for (int i = 0; i < objs[o].m; ++i) pl[pofs[o] + uint64_t(i)] = objs[o].shard_size;
+        }
+        for (uint64_t j = 0; j < dsum; ++j)
+            if (!data[j] && dl[j]) return set_error(MXEC_E_INVALID_ARG, "null data pointer " + std::to_string(j));
+        DevScope ds;
+        MXEC_TRY(ds.open(ctx, dev));
+        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
+        auto* recs = static_cast<LocateRec*>(out_dev);
+        // One launch per parity count m, as mxec_verify_batch_device.
+        std::map<int, std::vector<RsMixedObject>> groups;
+        return with_stable_coef(*ds.d, s, [&]() -> int {
+            groups.clear();
+            std::map<std::pair<int, int>, uint32_t> offs;
+            for (uint64_t o = 0; o < n_obj; ++o) {
+                const int k = objs[o].k, m = objs[o].m;
+                auto it = offs.find({k, m});
+                if (it == offs.end()) {
+                    uint32_t off = 0;
+                    MXEC_TRY(encode_coef(*ds.d, k, m, &off));
+                    it = offs.emplace(std::make_pair(k, m), off).first;
+                }
+                groups[m].push_back(RsMixedObject{k, objs[o].shard_size,
+                                                  RsObject{data + dofs[o], &dl[dofs[o]], &stored[pofs[o]],
+                                                           &pl[pofs[o]], it->second, nullptr, recs + o}});
+            }
+            return MXEC_OK;
+        }, [&]() -> int {
+            MXEC_HIP(launch_locate_init(recs, n_obj, s));
             return run_rs_mixed(*ds.d, *ds.slot, s, groups);
         });
     });

@@ -20,6 +20,14 @@ struct alignas(16) RsTileRec {  // one tile of a grouped launch (below)
     uint32_t in0;    // the object's first entry in in_ptrs / in_len
     uint32_t local;  // the tile's index within the object
 };
+// One object's result of a locate launch (mxec_locate_result's layout).
+struct LocateRec {
+    uint64_t first_bad;  // lowest bad byte column (atomic min)
+    uint64_t n_bad;      // bad byte columns (atomic add)
+    uint32_t shard_min;  // min / max of the columns' candidate shards
+    uint32_t shard_max;
+};
+constexpr uint32_t kLocateNoShard = 0xFFFFFFFEu;
 struct RsArgs {
     const uint8_t* const* in_ptrs;  // [n_obj][k]
     uint8_t* const* out_ptrs;       // [n_obj][r_total]; this launch writes rows
@@ -62,8 +70,21 @@ struct RsArgs {
     // caller fills the entries with 0xFF on the stream ahead of the launch.
     // Not with `multi`.
     uint64_t* const* first_bad = nullptr;
+    // Locate launch (mxec_locate) when set, instead of first_bad: the verify's
+    // walk (r == r_total <= 8, one row block), but a wave that finds a
+    // mismatch classifies each bad byte column and folds the result into
+    // locate[o], object o's record (initialised by launch_locate_init on the
+    // stream ahead of the launch).  loc_field: the field's log / exp tables,
+    // loc_tab + loc_off[o]: object o's (k, m) table (locate_plan.hpp); all
+    // three in device memory, uploaded with the descriptor tables.
+    LocateRec* const* locate = nullptr;
+    const uint8_t* loc_field = nullptr;
+    const uint8_t* loc_tab = nullptr;
+    const uint32_t* loc_off = nullptr;
 };
 constexpr uint32_t kMultiR = 4;
+// n records to the clean pattern {~0, 0, ~0, 0}.
+hipError_t launch_locate_init(LocateRec* recs, uint64_t n, hipStream_t s);
 
 // Tuning knobs of the interior kernel (tools/kernel_lab.cpp sweeps them).
 struct RsVariant {

@@ -11,6 +11,7 @@
 #include <map>
 
 #include "kernels.hpp"
+#include "locate_plan.hpp"
 #include "sha_plan.hpp"
 
 namespace mxec {
@@ -100,6 +101,17 @@ int decode_plan(Device& dev, int k, int m, const uint8_t* present, bool data_onl
     return MXEC_OK;
 }
 
+namespace {
+// A locate launch's (k, m) table into out (locate_table_bytes(m) bytes).
+int locate_table(int k, int m, uint8_t* out) {
+    auto mat = rs_matrix(k, m);
+    if (!mat) return set_error(MXEC_E_SINGULAR_MATRIX, "encoding matrix construction failed");
+    const int rc = locate_build_table(&mat->v[size_t(k) * size_t(k)], k, m, out);
+    if (rc) return set_error(rc, "locate: the parity rows do not tell the data shards apart");
+    return MXEC_OK;
+}
+}  // namespace
+
 int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, int r,
            const std::vector<RsObject>& objs, DescArena* arena, bool tune, uint32_t max_blocks) {
     if (objs.empty() || r == 0) return MXEC_OK;
@@ -132,9 +144,18 @@ int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, i
     const size_t o_outlen = w.add(8 * n * r);
     const size_t o_coef = w.add(4 * n);
     const size_t o_edge = w.add(8 * edges.size());
-    const bool verify = objs[0].first_bad != nullptr;
+    const bool locate = objs[0].locate != nullptr;  // r = m in 2..8: one row block
+    const bool verify = objs[0].first_bad != nullptr || locate;
     const size_t o_fb = verify ? w.add(sizeof(void*) * n) : 0;
+    const size_t o_lf = locate ? w.add(kLocateFieldBytes) : 0;
+    const size_t o_lt = locate ? w.add(locate_table_bytes(r)) : 0;
+    const size_t o_lo = locate ? w.add(4 * n) : 0;  // zero: one table
     char* hb = w.data();
+    if (locate) {
+        if (r < 2 || r > 8) return set_error(MXEC_E_INVALID_ARG, "locate needs 2..8 parity rows");
+        locate_field_tables(reinterpret_cast<uint8_t*>(hb + o_lf));
+        MXEC_TRY(locate_table(k, r, reinterpret_cast<uint8_t*>(hb + o_lt)));
+    }
     auto** ip = reinterpret_cast<const uint8_t**>(hb + o_in);
     auto** op = reinterpret_cast<uint8_t**>(hb + o_out);
     auto* il = reinterpret_cast<uint64_t*>(hb + o_inlen);
@@ -151,7 +172,7 @@ int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, i
             ol[o * r + i] = std::min<uint64_t>(ob.out_len[i], shard_size);
         }
         co[o] = ob.coef_off;
-        if (verify) reinterpret_cast<uint64_t**>(hb + o_fb)[o] = ob.first_bad;
+        if (verify) reinterpret_cast<void**>(hb + o_fb)[o] = locate ? ob.locate : static_cast<void*>(ob.first_bad);
     }
     if (!edges.empty()) std::memcpy(hb + o_edge, edges.data(), 8 * edges.size());
     char* db = nullptr;
@@ -172,7 +193,14 @@ int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, i
     a.r_total = uint32_t(r);
     a.aligned = aligned ? 1u : 0u;
     a.max_blocks = max_blocks ? max_blocks : dev.kn ? dev.kn->test_rs_grid : 0u;
-    if (verify) a.first_bad = reinterpret_cast<uint64_t* const*>(db + o_fb);
+    if (locate) {
+        a.locate = reinterpret_cast<LocateRec* const*>(db + o_fb);
+        a.loc_field = reinterpret_cast<const uint8_t*>(db + o_lf);
+        a.loc_tab = reinterpret_cast<const uint8_t*>(db + o_lt);
+        a.loc_off = reinterpret_cast<const uint32_t*>(db + o_lo);
+    } else if (verify) {
+        a.first_bad = reinterpret_cast<uint64_t* const*>(db + o_fb);
+    }
     if (max_blocks || verify) tune = false;  // the tuner times encodes and decodes only
     // Large aligned single-launch batches take the grid tuner's pick.
     GridTuner::Trial trial;
@@ -326,10 +354,12 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
     // r <= 8, index ranges that fit its 32-bit fields.  A call that is one
     // uniform group keeps the uniform kernel (no tile table).
     struct Plan {
-        int r;
-        const std::vector<RsMixedObject>* objs;
+        int r = 0;
+        const std::vector<RsMixedObject>* objs = nullptr;
         uint64_t sum_k = 0, n_tiles = 0, tile = 0;
         size_t o_in = 0, o_out = 0, o_inlen = 0, o_outlen = 0, o_coef = 0, o_tiles = 0, o_fb = 0;
+        size_t o_lt = 0, o_lo = 0;            // locate: the group's (k, m) tables, each object's offset
+        std::map<int, uint32_t> loc_of_k;     // k -> byte offset within o_lt
     };
     std::vector<Plan> grouped;
     std::vector<std::pair<int, const std::vector<RsMixedObject>*>> rest;
@@ -350,7 +380,9 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
         if (!un.empty()) rest.emplace_back(r, &un);
         if (al.empty()) continue;
         bool uniform = true;
-        Plan p{r, &al};
+        Plan p;
+        p.r = r;
+        p.objs = &al;
         p.tile = rs_tile_bytes(rs_group_variant(uint32_t(r)));
         for (const RsMixedObject& ob : al) {
             uniform &= ob.k == al[0].k && ob.shard_size == al[0].shard_size;
@@ -388,7 +420,8 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
     // multi-r launch instead (rs_apply_multi; MXEC_RS_MULTI=0 keeps one
     // launch per r).
     // A verify call (RsObject::first_bad) runs one launch per r.
-    const bool verify = (*grouped[0].objs)[0].o.first_bad != nullptr;
+    const bool locate = (*grouped[0].objs)[0].o.locate != nullptr;
+    const bool verify = (*grouped[0].objs)[0].o.first_bad != nullptr || locate;
     const bool multi_on = !verify && (!dev.kn || dev.kn->rs_multi);
     const uint32_t max_blocks = cap ? cap : dev.kn ? dev.kn->test_rs_grid : 0u;
     bool multi = multi_on && grouped.size() >= 2;
@@ -469,8 +502,25 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
         p.o_coef = w.add(4 * n);
         p.o_tiles = w.add(sizeof(RsTileRec) * p.n_tiles);
         if (verify) p.o_fb = w.add(sizeof(void*) * n);
+        if (locate) {
+            if (p.r < 2 || p.r > 8) return set_error(MXEC_E_INVALID_ARG, "locate needs 2..8 parity rows");
+            for (const RsMixedObject& ob : *p.objs)
+                if (!p.loc_of_k.count(ob.k)) {
+                    const uint32_t at = uint32_t(p.loc_of_k.size()) * locate_table_bytes(p.r);
+                    p.loc_of_k.emplace(ob.k, at);
+                }
+            p.o_lt = w.add(p.loc_of_k.size() * locate_table_bytes(p.r));
+            p.o_lo = w.add(4 * n);
+        }
     }
+    const size_t o_lf = locate ? w.add(kLocateFieldBytes) : 0;
     char* hb = w.data();
+    if (locate) {
+        locate_field_tables(reinterpret_cast<uint8_t*>(hb + o_lf));
+        for (const Plan& p : grouped)
+            for (const auto& kt : p.loc_of_k)
+                MXEC_TRY(locate_table(kt.first, p.r, reinterpret_cast<uint8_t*>(hb + p.o_lt + kt.second)));
+    }
     for (const Plan& p : grouped) {
         const int r = p.r;
         auto** ip = reinterpret_cast<const uint8_t**>(hb + p.o_in);
@@ -491,7 +541,8 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
                 ol[o * r + i] = std::min<uint64_t>(ob.o.out_len[i], ob.shard_size);
             }
             co[o] = ob.o.coef_off;
-            if (verify) reinterpret_cast<uint64_t**>(hb + p.o_fb)[o] = ob.o.first_bad;
+            if (verify) reinterpret_cast<void**>(hb + p.o_fb)[o] = locate ? ob.o.locate : static_cast<void*>(ob.o.first_bad);
+            if (locate) reinterpret_cast<uint32_t*>(hb + p.o_lo)[o] = p.loc_of_k.at(ob.k);
             const uint64_t nt = (ob.shard_size + p.tile - 1) / p.tile;
             for (uint64_t t = 0; t < nt; ++t)
                 tr[t0 + t] = RsTileRec{uint32_t(o), uint32_t(ob.k), uint32_t(in0), uint32_t(t)};
@@ -516,7 +567,14 @@ int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std
         a.tiles = reinterpret_cast<const RsTileRec*>(db + p.o_tiles);
         a.n_tiles = p.n_tiles;
         a.max_blocks = max_blocks;
-        if (verify) a.first_bad = reinterpret_cast<uint64_t* const*>(db + p.o_fb);
+        if (locate) {
+            a.locate = reinterpret_cast<LocateRec* const*>(db + p.o_fb);
+            a.loc_field = reinterpret_cast<const uint8_t*>(db + o_lf);
+            a.loc_tab = reinterpret_cast<const uint8_t*>(db + p.o_lt);
+            a.loc_off = reinterpret_cast<const uint32_t*>(db + p.o_lo);
+        } else if (verify) {
+            a.first_bad = reinterpret_cast<uint64_t* const*>(db + p.o_fb);
+        }
         MXEC_HIP(launch_rs_apply(a, dev.n_cus, s));
     }
     return w.finish(s);

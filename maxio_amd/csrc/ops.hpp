@@ -29,6 +29,13 @@ struct RsObject {
     // with 0xFF on the stream ahead of the call) receives per row the lowest
     // byte offset at which they differ (kernels.hpp RsArgs::first_bad).
     uint64_t* first_bad = nullptr;
+    // Locate (mxec_locate) when set instead, again for every object of the
+    // call or none: the verify's launch with r = m in 2..8 rows, but a
+    // mismatch is classified and folded into this device record (a
+    // LocateRec, kernels.hpp; initialised with launch_locate_init on the
+    // stream ahead of the call).  The launch uploads the (k, m) tables of
+    // locate_plan.hpp with its descriptor tables.
+    void* locate = nullptr;
 };
 
 // Applies each object's matrix; all objects share (k, r, shard_size).

@@ -30,6 +30,10 @@
 //  * ReedSolomon::verify is the same walk with the stores replaced by a
 //    compare against the stored parity (rs_tile's CMP policy, rs_verify_*):
 //    (k + r) x S bytes read, none written.
+//  * mxec_locate is that walk once more (the kLocate policy, rs_locate_*):
+//    all r syndromes stored ^ recomputed, one ballot per tile; only a wave
+//    that finds a mismatch goes on to name the shard each bad byte column
+//    points at.
 #include "kernels.hpp"
 
 #include <cstdlib>
@@ -211,22 +215,132 @@ __device__ __forceinline__ void report_first_bad(uint64_t* const* __restrict__ f
     atomicMin(reinterpret_cast<unsigned long long*>(*fbp + row), static_cast<unsigned long long>(at));
 }
 
+// What a tile does with its accumulators: the encode / decode stores them,
+// the verify compares them with the stored rows (report_first_bad), the
+// locate forms every row's syndrome and, on a mismatch, classifies each bad
+// byte column (below).
+enum : int { kStore = 0, kCmp = 1, kLocate = 2 };
+
+// Locate launches (RsArgs::locate set).  The walk, the loads and the masks
+// are the verify's; a wave whose syndromes are all zero (every wave of a
+// clean stripe) pays one ballot and writes nothing.  Otherwise each lane
+// classifies its bad byte columns -- columns whose syndrome bytes s_0..s_R-1
+// are not all zero -- and the wave folds its lanes' tallies into the
+// object's record with four atomics:
+//   exactly one s_i non-zero         -> parity shard k + i;
+//   all R non-zero, s = M[:, j] * e  -> data shard j, found without a search
+//       over k: s_1 / s_0 indexes the (k, m) table ratio -> j, rows 2..R-1
+//       are confirmed against log(M[i][j] / M[0][j]), and the column must lie
+//       below shard j's length (zero padding cannot be corrupt);
+//   anything else                    -> kLocateNoShard.
+// Tables: locate_plan.hpp.
+struct LocArgs {
+    LocateRec* const* rec = nullptr;  // [n_obj] (or the object's entry, inside a tile)
+    const uint8_t* field = nullptr;   // log [0, 256) | exp [256, 512)
+    const uint8_t* tab = nullptr;     // base of the (k, m) tables
+    const uint32_t* off = nullptr;    // [n_obj] byte offset of the object's table
+};
+
+struct LocTally {
+    uint32_t first = ~0u;  // lowest bad column, relative to the tile (or edge step)
+    uint32_t n = 0;        // bad columns
+    uint32_t cmin = ~0u, cmax = 0;
+};
+
+// One dword of every row's syndrome: d[i] holds bytes rel .. rel + 3 of row
+// i (rel: offset within the tile; col0: the same byte's offset in the shard).
+template <int R>
+__device__ __forceinline__ void locate_dword(LocTally& t, const uint32_t (&d)[R], uint32_t rel, uint64_t col0,
+                                             const uint8_t* __restrict__ field, const uint8_t* __restrict__ tab,
+                                             const uint64_t* __restrict__ il, uint32_t k) {
+    uint32_t any = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i) any |= d[i];
+    if (any == 0) return;
+#pragma unroll 1
+    for (uint32_t b = 0; b < 4; ++b) {
+        uint32_t s[R], nz = 0;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            s[i] = (d[i] >> (8 * b)) & 0xFFu;
+            nz += s[i] != 0;
+        }
+        if (nz == 0) continue;
+        uint32_t c = kLocateNoShard;
+        if (nz == 1) {
+#pragma unroll
+            for (int i = 0; i < R; ++i) c = s[i] ? k + uint32_t(i) : c;
+        } else if (nz == uint32_t(R)) {
+            if constexpr (R >= 2) {
+                const uint32_t l0 = field[s[0]];
+                uint32_t dl = uint32_t(field[s[1]]) + 255u - l0;
+                dl = dl >= 255u ? dl - 255u : dl;
+                const uint32_t j = tab[field[256 + dl]];
+                if (j < k) {  // 0xFF: no column has this ratio
+                    bool ok = col0 + b < il[j];
+#pragma unroll
+                    for (int i = 2; i < R; ++i) {
+                        uint32_t di = uint32_t(field[s[i]]) + 255u - l0;
+                        di = di >= 255u ? di - 255u : di;
+                        ok = ok && di == tab[256 * (1 + i) + j];
+                    }
+                    c = ok ? j : c;
+                }
+            }
+        }
+        t.n += 1;
+        t.first = min(t.first, rel + b);
+        t.cmin = min(t.cmin, c);
+        t.cmax = max(t.cmax, c);
+    }
+}
+
+// Every lane of the wave arrives here (the mismatch ballot is wave-uniform):
+// a butterfly over the 64 lanes, then lane 0's four atomics.
+__device__ __forceinline__ void locate_commit(LocateRec* rec, LocTally t, uint64_t base) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        t.first = min(t.first, uint32_t(__shfl_xor(t.first, o)));
+        t.n += uint32_t(__shfl_xor(t.n, o));
+        t.cmin = min(t.cmin, uint32_t(__shfl_xor(t.cmin, o)));
+        t.cmax = max(t.cmax, uint32_t(__shfl_xor(t.cmax, o)));
+    }
+    if ((threadIdx.x & 63u) != 0 || t.n == 0) return;
+    atomicMin(reinterpret_cast<unsigned long long*>(&rec->first_bad), static_cast<unsigned long long>(base + t.first));
+    atomicAdd(reinterpret_cast<unsigned long long*>(&rec->n_bad), static_cast<unsigned long long>(t.n));
+    atomicMin(&rec->shard_min, t.cmin);
+    atomicMax(&rec->shard_max, t.cmax);
+}
+
+__global__ void rs_locate_init(LocateRec* __restrict__ recs, uint64_t n) {
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < n) recs[i] = LocateRec{~uint64_t(0), 0, ~0u, 0};
+}
+
 // Edge tiles (launches with an unaligned pointer): the list entries
 // (object << 32 | tile index) are every tile of every object.  Each is walked in kEdgeTile steps with
 // byte-exact bounds on every input and output.  One step:
-template <int R, bool CMP = false>
+template <int R, int POL = kStore>
 __device__ __forceinline__ void edge_step(
     const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
     const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint64_t shard_size,
     uint32_t k, uint32_t r_total, uint32_t row0, const uint64_t* __restrict__ edge_list,
     uint32_t steps_per_tile, uint64_t tile_bytes, uint32_t aligned, uint64_t step,
-    uint64_t* const* __restrict__ fb_ptrs = nullptr) {
+    uint64_t* const* __restrict__ fb_ptrs = nullptr, LocArgs loc = {}) {
     const uint64_t e = edge_list[step / steps_per_tile];
     const uint32_t obj = uint32_t(e >> 32);
     const uint64_t col = uint64_t(uint32_t(e)) * tile_bytes + (step % steps_per_tile) * kEdgeTile +
                          threadIdx.x * 16;
-    if (col >= shard_size) return;
+    if constexpr (POL == kLocate) {
+        // Whole waves only: every lane takes part in locate_commit's
+        // butterfly.  A lane past the shard end has no valid byte in any
+        // input or row (the lengths are clamped to the shard size), so it
+        // loads nothing but the dummy and its syndrome is zero.
+        if (__builtin_amdgcn_ballot_w64(col < shard_size) == 0) return;
+    } else {
+        if (col >= shard_size) return;
+    }
     const uint32_t* __restrict__ tab = coef + coef_off[obj] + row0 * 8;
     uint32_t acc[1][4][R];
 #pragma unroll
@@ -274,6 +388,36 @@ __device__ __forceinline__ void edge_step(
         fixup(x[0], p, valid);
         mac_column<R, 1>(acc, x, tab + j * r_total * 8);
     }
+    if constexpr (POL == kLocate) {
+        // Every row's syndrome (cut at the row's length as the verify cuts
+        // it), one ballot, then the slow path.
+        uint32_t df[4][R], any = 0;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            uint64_t olen = out_len[uint64_t(obj) * r_total + row0 + i];
+            if (olen > shard_size) olen = shard_size;
+            const int64_t valid = col < olen ? int64_t(olen - col) : 0;
+            Vec4 st{{0, 0, 0, 0}};
+            if (valid > 0) st = load_partial(out_ptrs[uint64_t(obj) * r_total + row0 + i] + col, valid, aligned != 0);
+            Vec4 d{{acc[0][0][i] ^ st.w[0], acc[0][1][i] ^ st.w[1], acc[0][2][i] ^ st.w[2], acc[0][3][i] ^ st.w[3]}};
+            d = mask_tail(d, valid >= 16 ? 16 : int32_t(valid));
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                df[w][i] = d.w[w];
+                any |= d.w[w];
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(any != 0) == 0) return;
+        LocTally t;
+        const uint8_t* __restrict__ ktab = loc.tab + loc.off[obj];
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            locate_dword<R>(t, df[w], threadIdx.x * 16 + 4 * w, col + 4 * w, loc.field, ktab,
+                            in_len + uint64_t(obj) * k, k);
+        locate_commit(loc.rec[obj], t, col - threadIdx.x * 16);
+        return;
+    }
+    constexpr bool CMP = POL == kCmp;
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         uint64_t olen = out_len[uint64_t(obj) * r_total + row0 + i];
@@ -317,8 +461,21 @@ __global__ __launch_bounds__(kThreads) void rs_verify_edge(
     uint32_t steps_per_tile, uint64_t tile_bytes, uint32_t aligned, uint64_t n_steps,
     uint64_t* const* __restrict__ fb_ptrs) {
     for (uint64_t step = blockIdx.x; step < n_steps; step += gridDim.x)
-        edge_step<R, true>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, shard_size, k, r_total, row0,
+        edge_step<R, kCmp>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, shard_size, k, r_total, row0,
                            edge_list, steps_per_tile, tile_bytes, aligned, step, fb_ptrs);
+}
+
+// And for a locate launch.
+template <int R>
+__global__ __launch_bounds__(kThreads) void rs_locate_edge(
+    const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
+    const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
+    const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint64_t shard_size,
+    uint32_t k, uint32_t r_total, uint32_t row0, const uint64_t* __restrict__ edge_list,
+    uint32_t steps_per_tile, uint64_t tile_bytes, uint32_t aligned, uint64_t n_steps, LocArgs loc) {
+    for (uint64_t step = blockIdx.x; step < n_steps; step += gridDim.x)
+        edge_step<R, kLocate>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, shard_size, k, r_total, row0,
+                              edge_list, steps_per_tile, tile_bytes, aligned, step, nullptr, loc);
 }
 
 template <bool NT>
@@ -336,13 +493,16 @@ __device__ __forceinline__ Vec4 gload16_upto(gcptr p, int32_t valid, gcptr safe)
 // coefficient table at the first output row, input j's rows `stride` x 8
 // dwords apart.  CMP (verify launches): op are the stored rows, compared
 // with the accumulators instead of written; fbp points at the object's
-// first_bad pointer, `row` is the index of its first row there.
-template <int R, int V, bool NT, bool LNT = NT, int G = 4, bool CMP = false>
+// first_bad pointer, `row` is the index of its first row there.  kLocate
+// (locate launches): the stored rows loaded and cut the same way, then every
+// row's syndrome at once; loc.rec / loc.off point at the object's entries.
+template <int R, int V, bool NT, bool LNT = NT, int G = 4, int POL = kStore>
 __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, const uint64_t* __restrict__ il,
                                         uint8_t* const* __restrict__ op, const uint64_t* __restrict__ ol,
                                         const uint32_t* __restrict__ tab, uint32_t k, uint32_t stride,
                                         uint64_t base, gcptr safe, uint64_t* const* __restrict__ fbp = nullptr,
-                                        uint32_t row = 0) {
+                                        uint32_t row = 0, LocArgs loc = {}) {
+    constexpr bool CMP = POL != kStore;  // the stored rows are read, nothing is written
     constexpr uint32_t kTile = kThreads * 16 * V;
     const uint64_t end = base + kTile;
     const uint64_t lane = base + threadIdx.x * 16;
@@ -472,6 +632,32 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
                 }
             }
         }
+        if constexpr (POL == kLocate) {
+            // All R syndromes in place of the accumulators; a clean wave
+            // leaves after the one ballot.
+            uint32_t any = 0;
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+#pragma unroll
+                for (int v = 0; v < V; ++v)
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        acc[v][w][i] ^= st[i][v].w[w];
+                        any |= acc[v][w][i];
+                    }
+            if (__builtin_amdgcn_ballot_w64(any != 0) == 0) return;
+            LocTally t;
+            const uint8_t* __restrict__ ktab = loc.tab + *loc.off;
+#pragma unroll
+            for (int v = 0; v < V; ++v)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const uint32_t rel = uint32_t(lane_off) + uint32_t(v) * kThreads * 16 + 4 * w;
+                    locate_dword<R>(t, acc[v][w], rel, base + rel, loc.field, ktab, il, k);
+                }
+            locate_commit(*loc.rec, t, base);
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             uint32_t df[V][4], any = 0;
@@ -525,13 +711,13 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
 // the object), one wave-uniform scalar load, fetched one tile ahead so it
 // is in SGPRs when the tile starts (the uniform kernel computes the same
 // from the tile index).
-template <int R, int V, bool NT, bool GRP, bool LNT, int G, bool CMP>
+template <int R, int V, bool NT, bool GRP, bool LNT, int G, int POL>
 __device__ __forceinline__ void fast_tiles(
     const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
     const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
     uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
-    const RsTileRec* __restrict__ tiles, uint64_t* const* __restrict__ fb_ptrs) {
+    const RsTileRec* __restrict__ tiles, uint64_t* const* __restrict__ fb_ptrs, LocArgs loc = {}) {
     constexpr uint32_t kTile = kThreads * 16 * V;
     const gcptr safe = (gcptr)(reinterpret_cast<const uint8_t*>(coef));
     RsTileRec next{};
@@ -554,9 +740,14 @@ __device__ __forceinline__ void fast_tiles(
         }
         // Lengths are clamped to the shard size by the host, so a tile past
         // the shard end is cut by the same tests.
-        rs_tile<R, V, NT, LNT, G, CMP>(in_ptrs + in0, in_len + in0, out_ptrs + uint64_t(obj) * r_total + row0,
+        LocArgs lo = loc;
+        if constexpr (POL == kLocate) {
+            lo.rec = loc.rec + obj;
+            lo.off = loc.off + obj;
+        }
+        rs_tile<R, V, NT, LNT, G, POL>(in_ptrs + in0, in_len + in0, out_ptrs + uint64_t(obj) * r_total + row0,
                                        out_len + uint64_t(obj) * r_total + row0, coef + coef_off[obj] + row0 * 8, k,
-                                       r_total, base, safe, CMP ? fb_ptrs + obj : nullptr, row0);
+                                       r_total, base, safe, POL == kCmp ? fb_ptrs + obj : nullptr, row0, lo);
     }
 }
 
@@ -567,8 +758,8 @@ __global__ __launch_bounds__(kThreads, OCC) void rs_apply_fast(
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
     uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
     const RsTileRec* __restrict__ tiles) {
-    fast_tiles<R, V, NT, GRP, LNT, G, false>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform, r_total,
-                                             row0, tiles_per_obj, n_tiles, tiles, nullptr);
+    fast_tiles<R, V, NT, GRP, LNT, G, kStore>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform, r_total,
+                                              row0, tiles_per_obj, n_tiles, tiles, nullptr);
 }
 
 // ReedSolomon::verify: the encode's walk with the compare in place of the
@@ -582,8 +773,22 @@ __global__ __launch_bounds__(kThreads) void rs_verify_fast(
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
     uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
     const RsTileRec* __restrict__ tiles, uint64_t* const* __restrict__ fb_ptrs) {
-    fast_tiles<R, V, true, GRP, true, 4, true>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform,
+    fast_tiles<R, V, true, GRP, true, 4, kCmp>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform,
                                                r_total, row0, tiles_per_obj, n_tiles, tiles, fb_ptrs);
+}
+
+// mxec_locate: the verify's geometry and walk with the locate policy
+// (rs_tile kLocate).  Reads (k + r) x S bytes per object; writes only where
+// a syndrome is non-zero, into loc.rec[o].
+template <int R, int V, bool GRP>
+__global__ __launch_bounds__(kThreads) void rs_locate_fast(
+    const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
+    const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
+    const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
+    uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
+    const RsTileRec* __restrict__ tiles, LocArgs loc) {
+    fast_tiles<R, V, true, GRP, true, 4, kLocate>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform,
+                                                  r_total, row0, tiles_per_obj, n_tiles, tiles, nullptr, loc);
 }
 
 // One grouped launch for objects of every output count r <= kMultiR (a
@@ -638,10 +843,23 @@ hipError_t launch_fast(const RsArgs& a, uint32_t tiles_per_obj, uint64_t n_tiles
     return hipGetLastError();
 }
 
-// Verify launches (a.first_bad set): the shipping geometry of the same R.
+LocArgs loc_args(const RsArgs& a) { return LocArgs{a.locate, a.loc_field, a.loc_tab, a.loc_off}; }
+
+// Verify and locate launches (a.first_bad / a.locate set): the shipping
+// geometry of the same R.
 template <int R, int V, bool GRP>
 hipError_t launch_verify(const RsArgs& a, uint32_t tiles_per_obj, uint64_t n_tiles, uint64_t blocks,
                          hipStream_t s) {
+    if (a.locate) {  // the same geometry with the locate policy; one row block of 2..8 rows
+        if constexpr (R >= 2) {
+            if (a.row0 != 0 || a.r != a.r_total) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((rs_locate_fast<R, V, GRP>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
+                               a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
+                               tiles_per_obj, n_tiles, a.tiles, loc_args(a));
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;
+    }
     hipLaunchKernelGGL((rs_verify_fast<R, V, GRP>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
                        a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
                        tiles_per_obj, n_tiles, a.tiles, a.first_bad);
@@ -662,7 +880,7 @@ template <int R>
 hipError_t launch_grouped(const RsArgs& a, int n_cus, hipStream_t s) {
     const RsVariant v = rs_group_variant(uint32_t(R));
     const uint64_t blocks = grid_of(a, n_cus, v.blocks_per_cu, a.n_tiles);
-    if (a.first_bad) {
+    if (a.first_bad || a.locate) {
         if constexpr (R <= 4) {
             if (v.vecs == 4) return launch_verify<R, 4, true>(a, 0, a.n_tiles, blocks, s);
         }
@@ -682,7 +900,7 @@ hipError_t launch_r(const RsArgs& a, int n_cus, hipStream_t s, const RsVariant& 
         const uint64_t n_tiles = uint64_t(tiles_per_obj) * a.n_obj;
         const uint64_t blocks = grid_of(a, n_cus, var.blocks_per_cu, n_tiles);
         hipError_t e = hipErrorInvalidValue;
-        if (a.first_bad) {  // verify: the shipping geometries only
+        if (a.first_bad || a.locate) {  // verify, locate: the shipping geometries only
             if constexpr (R <= 4) {
                 if (var.vecs == 4) return launch_verify<R, 4, false>(a, tiles_per_obj, n_tiles, blocks, s);
             }
@@ -719,6 +937,17 @@ hipError_t launch_r(const RsArgs& a, int n_cus, hipStream_t s, const RsVariant& 
         const uint32_t steps = uint32_t(tile / kEdgeTile);
         const uint64_t n_steps = a.n_edge * steps;
         const uint64_t blocks = grid_of(a, n_cus, 8, n_steps);
+        if (a.locate) {
+            if constexpr (R >= 2) {
+                if (a.row0 != 0 || a.r != a.r_total) return hipErrorInvalidValue;
+                hipLaunchKernelGGL((rs_locate_edge<R>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s,
+                                   a.in_ptrs, a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off,
+                                   a.shard_size, a.k, a.r_total, a.row0, a.edge_list, steps, tile, a.aligned,
+                                   n_steps, loc_args(a));
+                return hipGetLastError();
+            }
+            return hipErrorInvalidValue;
+        }
         if (a.first_bad) {
             hipLaunchKernelGGL((rs_verify_edge<R>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s,
                                a.in_ptrs, a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off,
@@ -826,9 +1055,16 @@ hipError_t launch_rs_apply_variant(const RsArgs& a, int n_cus, hipStream_t s, co
     }
 }
 
+hipError_t launch_locate_init(LocateRec* recs, uint64_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (n > (uint64_t(1) << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rs_locate_init, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, recs, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_rs_apply(const RsArgs& a, int n_cus, hipStream_t s) {
     if (a.tiles && a.multi) {
-        if (!a.aligned || a.row0 != 0 || a.first_bad) return hipErrorInvalidValue;  // no multi-r verify
+        if (!a.aligned || a.row0 != 0 || a.first_bad || a.locate) return hipErrorInvalidValue;  // no multi-r verify
         if (a.n_tiles == 0) return hipSuccess;
         return launch_multi(a, n_cus, s);
     }

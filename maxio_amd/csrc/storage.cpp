@@ -800,6 +800,89 @@ extern "C" int mxec_scrub_object(mxec_ctx* ctx, const char* ec_dir, uint32_t fla
     });
 }
 
+// ---- locate / fast heal ------------------------------------------------------
+
+namespace {
+
+// The scrub's parity pass, naming the shard: no digest of any present shard.
+// A heal rebuilds the one located shard and hashes that alone.
+int locate_object(mxec_ctx* ctx, const fs::path& dir, uint32_t flags, mxec_locate_report* rep) {
+    Manifest man;
+    MXEC_TRY(read_manifest(dir, man));
+    const int k = int(man.chunk_count);
+    const int m = man.has_parity ? int(man.parity_shards) : 0;
+    const uint64_t shard = man.has_shard ? man.shard_size : man.chunk_size;
+    if (m > 0) {
+        const int rc = mxec_rs_check(k, m);
+        if (rc) return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
+    }
+    const int total = k + m;
+    if (int(man.chunks.size()) < total) return set_error(MXEC_E_JSON, "JSON error: manifest lists fewer shards than k+m");
+    rep->k = uint32_t(k);
+    rep->m = uint32_t(m);
+    rep->outcome = MXEC_LOCATE_SKIPPED;
+    if (m < 2 || m > 8) return MXEC_OK;
+
+    // Every shard file read and sized as scrub_object does; one that is
+    // missing or wrong-sized is the digest pass's to report.
+    std::vector<Bytes> bufs(static_cast<size_t>(total));
+    std::vector<uint8_t*> ptrs(static_cast<size_t>(total));
+    std::vector<size_t> lens(static_cast<size_t>(total));
+    bool whole = true;
+    for (int i = 0; i < total && whole; ++i) {
+        const size_t want = size_t(i < k ? std::min<uint64_t>(man.chunks[size_t(i)].size, shard) : shard);
+        Bytes& b = bufs[size_t(i)];
+        whole = read_file(dir / chunk_name(uint32_t(i)), b) == MXEC_OK && b.size() == want;
+        lens[size_t(i)] = want;
+        ptrs[size_t(i)] = b.data();
+    }
+    set_error(0, "");  // a missing file is a finding, not this call's error
+    if (!whole) return MXEC_OK;
+
+    mxec_locate_result res;
+    MXEC_TRY(mxec_locate(ctx, k, m, shard, ptrs.data(), lens.data(), ptrs.data() + k, &res));
+    rep->first_bad = res.first_bad;
+    rep->n_bad = res.n_bad;
+    rep->outcome = uint32_t(mxec_locate_outcome(&res, &rep->shard));
+    if (!(flags & MXEC_LOCATE_F_HEAL) || rep->outcome != MXEC_LOCATE_ONE) return MXEC_OK;
+
+    const int bad = int(rep->shard);
+    if (bad >= total) return MXEC_OK;
+    uint8_t expected[32];
+    if (!unhex32(man.chunks[size_t(bad)].sha256, expected)) return MXEC_OK;  // nothing to check a rebuild against
+    std::vector<uint8_t> present(static_cast<size_t>(total), 1);
+    present[size_t(bad)] = 0;
+    bufs[size_t(bad)].assign(lens[size_t(bad)], 0);
+    ptrs[size_t(bad)] = bufs[size_t(bad)].data();
+    // A zero-length shard has no buffer of its own; the decode wants a pointer.
+    uint8_t none = 0;
+    for (int i = 0; i < total; ++i)
+        if (!ptrs[size_t(i)]) ptrs[size_t(i)] = &none;
+    int np = 0;
+    MXEC_TRY(mxec_reconstruct(ctx, k, m, shard, ptrs.data(), lens.data(), nullptr, present.data(), 0, &np));
+    const uint8_t* hp = ptrs[size_t(bad)];
+    const size_t hl = lens[size_t(bad)];
+    uint8_t dig[32];
+    MXEC_TRY(mxec_sha256_batch(ctx, &hp, &hl, 1, reinterpret_cast<uint8_t(*)[32]>(dig)));
+    if (std::memcmp(dig, expected, 32) != 0) return MXEC_OK;  // more is wrong than one shard: the scrub's heal
+    MXEC_TRY(replace_file(dir, chunk_name(uint32_t(bad)), hp, hl));
+    rep->healed = 1;
+    return MXEC_OK;
+}
+
+}  // namespace
+
+extern "C" int mxec_locate_object(mxec_ctx* ctx, const char* ec_dir, uint32_t flags, void* out) {
+    return mxec::guarded([&]() -> int {
+        if (!ec_dir || !out) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        if (flags & ~MXEC_LOCATE_F_HEAL) return set_error(MXEC_E_INVALID_ARG, "locate: unknown flag");
+        auto* rep = static_cast<mxec_locate_report*>(out);
+        std::memset(rep, 0, sizeof *rep);
+        rep->first_bad = MXEC_VERIFY_OK;
+        return locate_object(ctx, fs::path(ec_dir), flags, rep);
+    });
+}
+
 // ---- VerifiedChunkReader (chunk_reader.rs:12-276) --------------------------
 
 namespace {

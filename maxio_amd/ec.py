@@ -56,6 +56,20 @@ VERIFY_OK = (1 << 64) - 1
 SCRUB_PARITY, SCRUB_DIGESTS, SCRUB_HEAL = 1, 2, 4
 SCRUB_CLEAN, SCRUB_DAMAGED, SCRUB_HEALED, SCRUB_UNRECOVERABLE = 0, 1, 2, 3
 SHARD_OK, SHARD_MISSING, SHARD_BAD_SIZE, SHARD_BAD_DIGEST, SHARD_HEALED = 0, 1, 2, 3, 0x80
+# mxec_locate / mxec_locate_object (MXEC_LOCATE_*)
+LOCATE_NO_SHARD = 0xFFFFFFFE
+LOCATE_CLEAN, LOCATE_ONE, LOCATE_MANY, LOCATE_SKIPPED = 0, 1, 2, 3
+LOCATE_F_HEAL = 1
+LOCATE_RESULT_BYTES = 24  # sizeof(mxec_locate_result): u64 first_bad, u64 n_bad, u32 shard_min, u32 shard_max
+
+
+def locate_outcome(first_bad: int, n_bad: int, shard_min: int, shard_max: int):
+    """mxec_locate_outcome over one record: (LOCATE_CLEAN | _ONE | _MANY,
+    the shard when ONE else None)."""
+    r = N.LocateResult(first_bad, n_bad, shard_min, shard_max)
+    shard = ctypes.c_uint32(0)
+    out = N.lib().mxec_locate_outcome(ctypes.byref(r), ctypes.byref(shard))
+    return out, (int(shard.value) if out == LOCATE_ONE else None)
 _SUM_BY_ALGO = {"CRC32": SUM_CRC32, "CRC32C": SUM_CRC32C, "SHA1": SUM_SHA1, "SHA256": SUM_SHA256}
 
 
@@ -313,6 +327,24 @@ class Context:
             _pp([_ptr(p) for p in par]), fb.ctypes.data_as(N.U64P), ctypes.byref(ok)))
         return bool(ok.value), [int(v) for v in fb[:m]]
 
+    def locate(self, data: Sequence, parity: Sequence, shard_size: int) -> dict:
+        """mxec_locate: which shard is damaged, from the parity alone (2 <= m
+        <= 8).  Returns first_bad, n_bad, shard_min, shard_max as the kernel
+        left them, plus outcome (LOCATE_CLEAN / _ONE / _MANY) and shard (the
+        damaged shard's index when ONE, else None)."""
+        arrs = [_u8(d) for d in data]
+        par = [_u8(p) for p in parity]
+        for p in par:
+            if p.size != shard_size:
+                raise RSError(-9, "parity shard is not shard_size bytes")
+        r = N.LocateResult()
+        _check(self._lib.mxec_locate(
+            self._h, len(arrs), len(par), shard_size, _pp([_ptr(a) for a in arrs]), _szp([a.size for a in arrs]),
+            _pp([_ptr(p) for p in par]), ctypes.byref(r)))
+        outcome, shard = locate_outcome(r.first_bad, r.n_bad, r.shard_min, r.shard_max)
+        return {"first_bad": int(r.first_bad), "n_bad": int(r.n_bad), "shard_min": int(r.shard_min),
+                "shard_max": int(r.shard_max), "outcome": outcome, "shard": shard}
+
     def reconstruct(self, shards: Sequence[Optional[object]], k: int, m: int, shard_size: int,
                     shard_len: Optional[Sequence[int]] = None,
                     expected: Optional[Sequence[bytes]] = None, data_only: bool = False):
@@ -444,6 +476,27 @@ class Context:
         pp = parity_ptrs if isinstance(parity_ptrs, ctypes.Array) else _pp(parity_ptrs)
         dl = None if data_len is None else (data_len if isinstance(data_len, ctypes.Array) else _u64p(data_len))
         _check(self._lib.mxec_verify_batch_device(self._h, dev, stream, arr, len(objs), dp, dl, pp, first_bad_ptr))
+
+    def locate_strided_device(self, k, m, shard_size, n_obj, data_ptr, data_obj_stride,
+                              data_shard_stride, parity_ptr, parity_obj_stride, parity_shard_stride,
+                              out_ptr, data_len=None, dev=0, stream=None):
+        """mxec_locate_strided_device: enqueue-only; out_ptr is a device array
+        of n_obj records of LOCATE_RESULT_BYTES, read after the stream has
+        drained."""
+        _check(self._lib.mxec_locate_strided_device(
+            self._h, dev, stream, k, m, shard_size, n_obj, data_ptr, data_obj_stride,
+            data_shard_stride, _u64p(data_len) if data_len is not None else None, parity_ptr,
+            parity_obj_stride, parity_shard_stride, out_ptr))
+
+    def locate_batch_device(self, objs: Sequence[tuple], data_ptrs, parity_ptrs, out_ptr, data_len=None,
+                            dev=0, stream=None):
+        """mxec_locate_batch_device: objects of mixed (k, m, shard_size), one
+        launch per m; out_ptr is a device array of len(objs) records."""
+        arr = objs if isinstance(objs, ctypes.Array) else (N.Object * len(objs))(*[N.Object(k, m, s) for (k, m, s) in objs])
+        dp = data_ptrs if isinstance(data_ptrs, ctypes.Array) else _pp(data_ptrs)
+        pp = parity_ptrs if isinstance(parity_ptrs, ctypes.Array) else _pp(parity_ptrs)
+        dl = None if data_len is None else (data_len if isinstance(data_len, ctypes.Array) else _u64p(data_len))
+        _check(self._lib.mxec_locate_batch_device(self._h, dev, stream, arr, len(objs), dp, dl, pp, out_ptr))
 
     def encode_batch_host(self, objs: Sequence[tuple], data_ptrs, parity_ptrs, data_len=None,
                           digests: Optional[np.ndarray] = None, return_rc: bool = False):
@@ -769,6 +822,17 @@ class Context:
                 "parity_first_bad": int(r.parity_first_bad),
                 "shard_state": [int(x) for x in r.shard_state[: r.k + r.m]]}
 
+    def locate_object(self, ec_dir: str, heal: bool = False) -> dict:
+        """mxec_locate_object over one `{key}.ec` directory: the parity pass
+        that names the damaged shard (no SHA-256 of any present shard).
+        heal: on outcome LOCATE_ONE rebuild that shard, hash it alone against
+        the manifest and rewrite it.  Returns the report as a dict."""
+        r = N.LocateReport()
+        _check(self._lib.mxec_locate_object(self._h, ec_dir.encode(), LOCATE_F_HEAL if heal else 0, ctypes.byref(r)))
+        return {"k": int(r.k), "m": int(r.m), "outcome": int(r.outcome),
+                "shard": int(r.shard) if r.outcome == LOCATE_ONE else None,
+                "first_bad": int(r.first_bad), "n_bad": int(r.n_bad), "healed": int(r.healed)}
+
     def try_reconstruct_data_chunk(self, ec_dir: str, target: int, capacity: int = 1 << 26) -> bytes:
         out = np.zeros(max(1, capacity), np.uint8)
         n = ctypes.c_uint64(0)
@@ -901,6 +965,12 @@ class ReedSolomon:
         size = self._check_shards(shards)
         ok, _ = self.ctx.verify(shards[: self.k], shards[self.k:], size)
         return ok
+
+    def locate(self, shards: list) -> dict:
+        """Which shard is damaged, from the parity alone (Context.locate);
+        needs 2 <= m <= 8.  Not in the crate."""
+        size = self._check_shards(shards)
+        return self.ctx.locate(shards[: self.k], shards[self.k:], size)
 
     def _reconstruct(self, shards: list, data_only: bool) -> None:
         size = self._check_shards(shards, allow_none=True)

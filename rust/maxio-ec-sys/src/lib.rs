@@ -122,6 +122,39 @@ pub const MXEC_SHARD_BAD_SIZE: u8 = 2;
 pub const MXEC_SHARD_BAD_DIGEST: u8 = 3;
 pub const MXEC_SHARD_HEALED: u8 = 0x80;
 
+/// `mxec_locate_result`: one object's record of `mxec_locate*` (their `out` /
+/// `out_dev` argument; `mxec_locate_outcome` reads it).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct MxecLocateResult {
+    pub first_bad: u64,
+    pub n_bad: u64,
+    pub shard_min: u32,
+    pub shard_max: u32,
+}
+
+/// `mxec_locate_report`: what `mxec_locate_object` found (its `out` argument).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct MxecLocateReport {
+    pub k: u32,
+    pub m: u32,
+    pub outcome: u32,
+    pub shard: u32,
+    pub first_bad: u64,
+    pub n_bad: u64,
+    pub healed: u32,
+    pub reserved: u32,
+}
+
+// ---- mxec_locate* candidates, outcomes and flags ------------------------------
+pub const MXEC_LOCATE_NO_SHARD: u32 = 0xFFFFFFFE;
+pub const MXEC_LOCATE_CLEAN: u32 = 0;
+pub const MXEC_LOCATE_ONE: u32 = 1;
+pub const MXEC_LOCATE_MANY: u32 = 2;
+pub const MXEC_LOCATE_SKIPPED: u32 = 3;
+pub const MXEC_LOCATE_F_HEAL: u32 = 1;
+
 // ---- mxec_ctx_pipe_stats counter indices ----------------------------------
 pub const MXEC_PIPE_STAT_COPIES_1D: c_int = 0;
 pub const MXEC_PIPE_STAT_COPIES_2D: c_int = 1;
@@ -248,6 +281,15 @@ extern "C" {
     pub fn mxec_reader_close(r: *mut MxecReader);
     /// `out`: a `*mut MxecScrubReport`.
     pub fn mxec_scrub_object(ctx: *mut MxecCtx, ec_dir: *const c_char, flags: u32, out: *mut c_void) -> c_int;
+    /// `result`: a `*const MxecLocateResult`.
+    pub fn mxec_locate_outcome(result: *const c_void, shard: *mut u32) -> c_int;
+    /// `out`: a `*mut MxecLocateResult`.
+    pub fn mxec_locate(ctx: *mut MxecCtx, k: c_int, m: c_int, shard_size: usize, data: *const *const u8, data_len: *const usize, parity: *const *const u8, out: *mut c_void) -> c_int;
+    /// `out_dev`: a device array of `n_obj` `MxecLocateResult`.
+    pub fn mxec_locate_strided_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, k: c_int, m: c_int, shard_size: u64, n_obj: u64, data: *const u8, data_obj_stride: u64, data_shard_stride: u64, data_len: *const u64, parity: *const u8, parity_obj_stride: u64, parity_shard_stride: u64, out_dev: *mut c_void) -> c_int;
+    pub fn mxec_locate_batch_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, objs: *const MxecObject, n_obj: u64, data: *const *const u8, data_len: *const u64, parity: *const *const u8, out_dev: *mut c_void) -> c_int;
+    /// `out`: a `*mut MxecLocateReport`.
+    pub fn mxec_locate_object(ctx: *mut MxecCtx, ec_dir: *const c_char, flags: u32, out: *mut c_void) -> c_int;
     pub fn mxec_try_reconstruct_data_chunk(ctx: *mut MxecCtx, ec_dir: *const c_char, target: u32, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
 }
 
