@@ -1,9 +1,9 @@
-// capi.cpp — extern "C" entry points of include/maxio_ec.h (context, host
-// pointer drop-ins, device-resident batches).  No exception crosses the ABI.
+// capi.cpp — extern "C" entry points of include/maxio_ec.h: context, stats,
+// host memory, SHA-256 batches and the reconstructs (the parity pass, encode /
+// verify / locate, is parity_pass.cpp).  No exception crosses the ABI.
 #include <algorithm>
 #include <array>
 #include <cctype>
-#include <chrono>
 #include <fstream>
 #include <cstdio>
 #include <cstdlib>
@@ -18,26 +18,11 @@
 
 #include "../../include/maxio_ec.h"
 #include "kernels.hpp"
-#include "locate_plan.hpp"
 #include "ops.hpp"
 
 using namespace mxec;
 
 namespace {
-
-// MXEC_PIPE_COPY (knobs.hpp): whether a host-pointer call's copies of
-// mxec_host_alloc memory may go by CU-wave copy kernels -- the reconstruct /
-// hash (GET) paths under auto and waves, the encode (PUT) path under waves
-// only (copy_watch.hpp has the measurements behind the split).
-bool copy_waves_get(const Device& d) {
-    if (!d.kn) return false;
-    if (d.kn->pipe_copy == 1) return true;
-    if (d.kn->pipe_copy != 2) return false;
-    const int64_t now = std::chrono::duration_cast<std::chrono::nanoseconds>(
-                            std::chrono::steady_clock::now().time_since_epoch()).count();
-    return now < d.waves_up_until_ns.load() || now < d.waves_down_until_ns.load();
-}
-bool copy_waves_put(const Device& d) { return d.kn && d.kn->pipe_copy == 1; }
 
 // One object of a device-resident reconstruct batch (device shard pointers).
 struct BatchObj {
@@ -109,6 +94,49 @@ int rebuild_batch(Device& d, Slot& slot, hipStream_t s, bool data_only, const st
         if (plans[t])
             for (int e : plans[t]->missing) all[which[t]].present[e] = 1;
     return MXEC_OK;
+}
+
+// Hashes device shards `ptrs` in one launch on `s` and compares on the device
+// (the verify kernel compares message t against expected_dev[idx[t]]); the
+// flags and the stream form's timeout word are read back, and a mismatch is
+// an erasure: present[idx[t]] = 0 (chunk_reader.rs:176-196).
+int verify_digests_device(Device& d, Slot& slot, hipStream_t s, const std::vector<const uint8_t*>& ptrs,
+                          const std::vector<uint64_t>& lens, const std::vector<uint64_t>& idx,
+                          const uint8_t* expected_dev, uint8_t* present) {
+    MXEC_TRY(slot.digests.grow(ptrs.size()));
+    auto* ok = static_cast<uint8_t*>(slot.digests.p);
+    const uint32_t* tmo = nullptr;
+    MXEC_TRY(run_sha(d, slot, s, ptrs, lens, nullptr, expected_dev, ok, &idx, nullptr, 0, &tmo));
+    const size_t fo = (ptrs.size() + 15) & ~size_t(15);
+    MXEC_TRY(slot.hdig.grow(fo + 16));
+    auto* hflag = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(slot.hdig.p) + fo);
+    *hflag = 0;
+    MXEC_HIP(hipMemcpyAsync(slot.hdig.p, ok, ptrs.size(), hipMemcpyDeviceToHost, s));
+    if (tmo) MXEC_HIP(hipMemcpyAsync(hflag, tmo, 4, hipMemcpyDeviceToHost, s));
+    MXEC_TRY(slot_wait(slot, s));
+    if (*hflag != 0)
+        return set_error(MXEC_E_DEVICE, "SHA-256 stream kernel: a wave timed out waiting for its predecessor segment");
+    const auto* okh = static_cast<const uint8_t*>(slot.hdig.p);
+    for (size_t t = 0; t < idx.size(); ++t)
+        if (!okh[t]) present[idx[t]] = 0;
+    return MXEC_OK;
+}
+
+// The end of a batch reconstruct: every object's status out, and the first
+// failing object's as the call's own, with chunk_reader.rs's message.
+int batch_status(const std::vector<BatchObj>& bo, const std::vector<int32_t>& st, int32_t* status_out) {
+    int first_err = MXEC_OK;
+    for (size_t o = 0; o < bo.size(); ++o) {
+        if (status_out) status_out[o] = st[o];
+        if (st[o] != MXEC_OK && first_err == MXEC_OK) {
+            const int total = bo[o].k + bo[o].m;
+            int np = 0;
+            for (int i = 0; i < total; ++i) np += bo[o].present[i] != 0;
+            first_err = st[o];
+            set_error(first_err, too_few_msg(np, bo[o].k, total));
+        }
+    }
+    return first_err;
 }
 
 }  // namespace
@@ -454,56 +482,6 @@ int mxec_sha256_batch(mxec_ctx* ctx, const uint8_t* const* bufs, const size_t* l
     });
 }
 
-int mxec_encode(mxec_ctx* ctx, int k, int m, size_t shard_size, const uint8_t* const* data,
-                const size_t* data_len, uint8_t* const* parity, uint8_t (*sha256_out)[32]) {
-    return guarded([&] {
-        MXEC_TRY(check_km(k, m));
-        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-        if (!data || !parity) return set_error(MXEC_E_INVALID_ARG, "null shard array");
-        std::vector<uint64_t> len(static_cast<size_t>(k + m), shard_size);
-        for (int j = 0; j < k; ++j) {
-            len[size_t(j)] = data_len ? data_len[j] : shard_size;
-            if (len[size_t(j)] > shard_size)
-                return set_error(MXEC_E_INCORRECT_SHARD_SIZE, "data chunk longer than shard_size");
-            if (len[size_t(j)] && !data[j]) return set_error(MXEC_E_INVALID_ARG, "null data chunk");
-        }
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, -1));
-        Slot& slot = *ds.slot;
-        hipStream_t s = slot.stream;
-        const uint64_t sa = round_up(shard_size, kSlotAlign);
-        MXEC_TRY(slot.shards.ensure(sa * uint64_t(k + m)));
-        auto* base = static_cast<uint8_t*>(slot.shards.p);
-        std::vector<const uint8_t*> in(static_cast<size_t>(k));
-        std::vector<uint8_t*> out(static_cast<size_t>(m));
-        std::vector<UploadSeg> up;
-        for (int j = 0; j < k; ++j) {
-            in[size_t(j)] = base + sa * uint64_t(j);
-            if (len[size_t(j)]) up.push_back({sa * uint64_t(j), data[j], len[size_t(j)]});
-        }
-        MXEC_TRY(upload_segments(slot, s, base, up, copy_waves_put(*ds.d)));
-        for (int i = 0; i < m; ++i) out[size_t(i)] = base + sa * uint64_t(k + i);
-        uint32_t off = 0;
-        MXEC_TRY(with_stable_coef(
-            *ds.d, s, [&] { return encode_coef(*ds.d, k, m, &off); },
-            [&] {
-                RsObject ob{in.data(), len.data(), out.data(), len.data() + k, off};
-                return run_rs(*ds.d, slot, s, shard_size, k, m, {ob});
-            }));
-        std::vector<DownloadSeg> down;
-        for (int i = 0; i < m; ++i) down.push_back({sa * uint64_t(k + i), parity[i], shard_size});
-        MXEC_TRY(download_segments(slot, s, base, down, copy_waves_put(*ds.d)));
-        if (sha256_out) {
-            // write_chunk / compute_and_write_parity digests (filesystem.rs:1070,
-            // :1131), combined with every concurrent caller's verification work.
-            std::vector<const uint8_t*> ptrs(in.begin(), in.end());
-            for (auto* p : out) ptrs.push_back(p);
-            return sha256_combined(*ds.d, slot, s, ptrs, len, &sha256_out[0][0]);
-        }
-        return MXEC_OK;
-    });
-}
-
 int mxec_reconstruct(mxec_ctx* ctx, int k, int m, size_t shard_size, uint8_t* const* shards,
                      const size_t* shard_len, const uint8_t (*expected_sha256)[32],
                      uint8_t* present_inout, uint32_t flags, int* n_present) {
@@ -596,447 +574,6 @@ int mxec_reconstruct(mxec_ctx* ctx, int k, int m, size_t shard_size, uint8_t* co
     });
 }
 
-int mxec_encode_strided_device(mxec_ctx* ctx, int dev, void* stream, int k, int m,
-                               uint64_t shard_size, uint64_t n_obj, const uint8_t* data,
-                               uint64_t data_obj_stride, uint64_t data_shard_stride,
-                               const uint64_t* data_len, uint8_t* parity,
-                               uint64_t parity_obj_stride, uint64_t parity_shard_stride,
-                               uint8_t* digests_dev) {
-    return guarded([&] {
-        MXEC_TRY(check_km(k, m));
-        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-        if (n_obj == 0) return MXEC_OK;
-        if (!data || !parity) return set_error(MXEC_E_INVALID_ARG, "null base pointer");
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, dev));
-        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-        uint32_t off = 0;
-        std::vector<uint64_t> len(static_cast<size_t>(k + m), shard_size);
-        for (int j = 0; j < k; ++j)
-            if (data_len) len[size_t(j)] = std::min<uint64_t>(data_len[j], shard_size);
-        std::vector<const uint8_t*> in(static_cast<size_t>(n_obj * k));
-        std::vector<uint8_t*> out(static_cast<size_t>(n_obj * m));
-        std::vector<RsObject> objs(static_cast<size_t>(n_obj));
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            for (int j = 0; j < k; ++j) in[o * k + j] = data + o * data_obj_stride + j * data_shard_stride;
-            for (int i = 0; i < m; ++i) out[o * m + i] = parity + o * parity_obj_stride + i * parity_shard_stride;
-            objs[o] = RsObject{&in[o * k], len.data(), &out[o * m], len.data() + k, 0};
-        }
-        MXEC_TRY(with_stable_coef(
-            *ds.d, s, [&] { return encode_coef(*ds.d, k, m, &off); },
-            [&] {
-                for (auto& ob : objs) ob.coef_off = off;
-                return run_rs(*ds.d, *ds.slot, s, shard_size, k, m, objs);
-            }));
-        if (digests_dev) {
-            std::vector<const uint8_t*> ptrs;
-            std::vector<uint64_t> lens;
-            ptrs.reserve(size_t(n_obj * (k + m)));
-            lens.reserve(ptrs.capacity());
-            for (uint64_t o = 0; o < n_obj; ++o) {
-                for (int j = 0; j < k; ++j) { ptrs.push_back(in[o * k + j]); lens.push_back(len[size_t(j)]); }
-                for (int i = 0; i < m; ++i) { ptrs.push_back(out[o * m + i]); lens.push_back(shard_size); }
-            }
-            MXEC_TRY(run_sha(*ds.d, *ds.slot, s, ptrs, lens, digests_dev, nullptr, nullptr));
-        }
-        return MXEC_OK;
-    });
-}
-
-int mxec_encode_batch_device(mxec_ctx* ctx, int dev, void* stream, const mxec_object* objs,
-                             uint64_t n_obj, const uint8_t* const* data, const uint64_t* data_len,
-                             uint8_t* const* parity, uint8_t* digests_dev) {
-    return guarded([&] {
-        if (n_obj == 0) return MXEC_OK;
-        if (!objs || !data || !parity) return set_error(MXEC_E_INVALID_ARG, "null argument");
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, dev));
-        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-        std::vector<uint64_t> dofs(static_cast<size_t>(n_obj)), pofs(static_cast<size_t>(n_obj));
-        uint64_t dsum = 0, psum = 0;
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            MXEC_TRY(check_km(objs[o].k, objs[o].m));
-            if (objs[o].shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-            dofs[o] = dsum;
-            pofs[o] = psum;
-            dsum += uint64_t(objs[o].k);
-            psum += uint64_t(objs[o].m);
-        }
-        for (uint64_t i = 0; i < psum; ++i)
-            if (!parity[i]) return set_error(MXEC_E_INVALID_ARG, "null parity pointer " + std::to_string(i));
-        std::vector<uint64_t> dl(static_cast<size_t>(dsum)), pl(static_cast<size_t>(psum));
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            for (int j = 0; j < objs[o].k; ++j) {
-                const uint64_t idx = dofs[o] + uint64_t(j);
-                dl[idx] = data_len ? std::min<uint64_t>(data_len[idx], objs[o].shard_size) : objs[o].shard_size;
-            }
-            for (int i = 0; i < objs[o].m; ++i) pl[pofs[o] + uint64_t(i)] = objs[o].shard_size;
-        }
-        for (uint64_t j = 0; j < dsum; ++j)
-            if (!data[j] && dl[j]) return set_error(MXEC_E_INVALID_ARG, "null data pointer " + std::to_string(j));
-        // One launch per parity count m: objects of every k and shard size
-        // share it (run_rs_mixed; unaligned or m > 8: per (k, shard_size)).
-        std::map<int, std::vector<RsMixedObject>> groups;
-        MXEC_TRY(with_stable_coef(*ds.d, s, [&]() -> int {
-            groups.clear();
-            std::map<std::pair<int, int>, uint32_t> offs;
-            for (uint64_t o = 0; o < n_obj; ++o) {
-                const int k = objs[o].k, m = objs[o].m;
-                auto it = offs.find({k, m});
-                if (it == offs.end()) {
-                    uint32_t off = 0;
-                    MXEC_TRY(encode_coef(*ds.d, k, m, &off));
-                    it = offs.emplace(std::make_pair(k, m), off).first;
-                }
-                groups[m].push_back(RsMixedObject{k, objs[o].shard_size,
-                                                  RsObject{data + dofs[o], &dl[dofs[o]], parity + pofs[o],
-                                                           &pl[pofs[o]], it->second}});
-            }
-            return MXEC_OK;
-        }, [&] { return run_rs_mixed(*ds.d, *ds.slot, s, groups); }));
-        if (digests_dev) {
-            std::vector<const uint8_t*> ptrs;
-            std::vector<uint64_t> lens;
-            for (uint64_t o = 0; o < n_obj; ++o) {
-                for (int j = 0; j < objs[o].k; ++j) { ptrs.push_back(data[dofs[o] + j]); lens.push_back(dl[dofs[o] + j]); }
-                for (int i = 0; i < objs[o].m; ++i) { ptrs.push_back(parity[pofs[o] + i]); lens.push_back(objs[o].shard_size); }
-            }
-            MXEC_TRY(run_sha(*ds.d, *ds.slot, s, ptrs, lens, digests_dev, nullptr, nullptr));
-        }
-        return MXEC_OK;
-    });
-}
-
-int mxec_verify(mxec_ctx* ctx, int k, int m, size_t shard_size, const uint8_t* const* data,
-                const size_t* data_len, const uint8_t* const* parity, uint64_t* first_bad, int* consistent) {
-    return guarded([&] {
-        MXEC_TRY(check_km(k, m));
-        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-        if (!data || !parity) return set_error(MXEC_E_INVALID_ARG, "null shard array");
-        std::vector<uint64_t> len(static_cast<size_t>(k + m), shard_size);
-        for (int j = 0; j < k; ++j) {
-            len[size_t(j)] = data_len ? data_len[j] : shard_size;
-            if (len[size_t(j)] > shard_size)
-                return set_error(MXEC_E_INCORRECT_SHARD_SIZE, "data chunk longer than shard_size");
-            if (len[size_t(j)] && !data[j]) return set_error(MXEC_E_INVALID_ARG, "null data chunk");
-        }
-        for (int i = 0; i < m; ++i)
-            if (!parity[i]) return set_error(MXEC_E_INVALID_ARG, "null parity shard");
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, -1));
-        Slot& slot = *ds.slot;
-        hipStream_t s = slot.stream;
-        // The shards as mxec_encode stages them, then the m result entries.
-        const uint64_t sa = round_up(shard_size, kSlotAlign);
-        const uint64_t fb_off = sa * uint64_t(k + m);
-        MXEC_TRY(slot.shards.ensure(fb_off + 8 * uint64_t(m)));
-        auto* base = static_cast<uint8_t*>(slot.shards.p);
-        auto* fb = reinterpret_cast<uint64_t*>(base + fb_off);
-        std::vector<const uint8_t*> in(static_cast<size_t>(k));
-        std::vector<uint8_t*> stored(static_cast<size_t>(m));
-        std::vector<UploadSeg> up;
-        for (int j = 0; j < k; ++j) {
-            in[size_t(j)] = base + sa * uint64_t(j);
-            if (len[size_t(j)]) up.push_back({sa * uint64_t(j), data[j], len[size_t(j)]});
-        }
-        for (int i = 0; i < m; ++i) {
-            stored[size_t(i)] = base + sa * uint64_t(k + i);
-            up.push_back({sa * uint64_t(k + i), parity[i], shard_size});
-        }
-        MXEC_TRY(upload_segments(slot, s, base, up, copy_waves_get(*ds.d)));
-        uint32_t off = 0;
-        MXEC_TRY(with_stable_coef(
-            *ds.d, s, [&] { return encode_coef(*ds.d, k, m, &off); },
-            [&] {
-                MXEC_HIP(hipMemsetAsync(fb, 0xFF, 8 * size_t(m), s));
-                RsObject ob{in.data(), len.data(), stored.data(), len.data() + k, off, fb};
-                return run_rs(*ds.d, slot, s, shard_size, k, m, {ob});
-            }));
-        std::vector<uint64_t> res(static_cast<size_t>(m));
-        std::vector<DownloadSeg> down{{fb_off, reinterpret_cast<uint8_t*>(res.data()), 8 * uint64_t(m)}};
-        MXEC_TRY(download_segments(slot, s, base, down, false));
-        bool ok = true;
-        for (int i = 0; i < m; ++i) ok = ok && res[size_t(i)] == MXEC_VERIFY_OK;
-        if (first_bad) std::memcpy(first_bad, res.data(), 8 * size_t(m));
-        if (consistent) *consistent = ok ? 1 : 0;
-        return MXEC_OK;
-    });
-}
-
-int mxec_verify_strided_device(mxec_ctx* ctx, int dev, void* stream, int k, int m, uint64_t shard_size,
-                               uint64_t n_obj, const uint8_t* data, uint64_t data_obj_stride,
-                               uint64_t data_shard_stride, const uint64_t* data_len, const uint8_t* parity,
-                               uint64_t parity_obj_stride, uint64_t parity_shard_stride,
-                               uint64_t* first_bad_dev) {
-    return guarded([&] {
-        MXEC_TRY(check_km(k, m));
-        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-        if (n_obj == 0) return MXEC_OK;
-        if (!data || !parity) return set_error(MXEC_E_INVALID_ARG, "null base pointer");
-        if (!first_bad_dev) return set_error(MXEC_E_INVALID_ARG, "null first_bad array");
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, dev));
-        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-        uint32_t off = 0;
-        std::vector<uint64_t> len(static_cast<size_t>(k + m), shard_size);
-        for (int j = 0; j < k; ++j)
-            if (data_len) len[size_t(j)] = std::min<uint64_t>(data_len[j], shard_size);
-        std::vector<const uint8_t*> in(static_cast<size_t>(n_obj * k));
-        std::vector<uint8_t*> stored(static_cast<size_t>(n_obj * m));  // read only (RsObject::first_bad)
-        std::vector<RsObject> objs(static_cast<size_t>(n_obj));
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            for (int j = 0; j < k; ++j) in[o * k + j] = data + o * data_obj_stride + j * data_shard_stride;
-            for (int i = 0; i < m; ++i)
-                stored[o * m + i] = const_cast<uint8_t*>(parity) + o * parity_obj_stride + i * parity_shard_stride;
-            objs[o] = RsObject{&in[o * k], len.data(), &stored[o * m], len.data() + k, 0, first_bad_dev + o * m};
-        }
-        return with_stable_coef(
-            *ds.d, s, [&] { return encode_coef(*ds.d, k, m, &off); },
-            [&] {
-                // Filled inside the launch step: a pass queued again after a
-                // table recycle (with_stable_coef) starts from clean entries.
-                MXEC_HIP(hipMemsetAsync(first_bad_dev, 0xFF, size_t(8 * n_obj * uint64_t(m)), s));
-                for (auto& ob : objs) ob.coef_off = off;
-                return run_rs(*ds.d, *ds.slot, s, shard_size, k, m, objs);
-            });
-    });
-}
-
-int mxec_verify_batch_device(mxec_ctx* ctx, int dev, void* stream, const mxec_object* objs, uint64_t n_obj,
-                             const uint8_t* const* data, const uint64_t* data_len,
-                             const uint8_t* const* parity, uint64_t* first_bad_dev) {
-    return guarded([&] {
-        if (n_obj == 0) return MXEC_OK;
-        if (!objs || !data || !parity || !first_bad_dev) return set_error(MXEC_E_INVALID_ARG, "null argument");
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, dev));
-        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-        std::vector<uint64_t> dofs(static_cast<size_t>(n_obj)), pofs(static_cast<size_t>(n_obj));
-        uint64_t dsum = 0, psum = 0;
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            MXEC_TRY(check_km(objs[o].k, objs[o].m));
-            if (objs[o].shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-            dofs[o] = dsum;
-            pofs[o] = psum;
-            dsum += uint64_t(objs[o].k);
-            psum += uint64_t(objs[o].m);
-        }
-        std::vector<uint8_t*> stored(static_cast<size_t>(psum));  // read only (RsObject::first_bad)
-        for (uint64_t i = 0; i < psum; ++i) {
-            if (!parity[i]) return set_error(MXEC_E_INVALID_ARG, "null parity pointer " + std::to_string(i));
-            stored[i] = const_cast<uint8_t*>(parity[i]);
-        }
-        std::vector<uint64_t> dl(static_cast<size_t>(dsum)), pl(static_cast<size_t>(psum));
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            for (int j = 0; j < objs[o].k; ++j) {
-                const uint64_t idx = dofs[o] + uint64_t(j);
-                dl[idx] = data_len ? std::min<uint64_t>(data_len[idx], objs[o].shard_size) : objs[o].shard_size;
-            }
-            for (int i = 0; i < objs[o].m; ++i) pl[pofs[o] + uint64_t(i)] = objs[o].shard_size;
-        }
-        for (uint64_t j = 0; j < dsum; ++j)
-            if (!data[j] && dl[j]) return set_error(MXEC_E_INVALID_ARG, "null data pointer " + std::to_string(j));
-        // One launch per parity count m, as mxec_encode_batch_device.
-        std::map<int, std::vector<RsMixedObject>> groups;
-        return with_stable_coef(*ds.d, s, [&]() -> int {
-            groups.clear();
-            std::map<std::pair<int, int>, uint32_t> offs;
-            for (uint64_t o = 0; o < n_obj; ++o) {
-                const int k = objs[o].k, m = objs[o].m;
-                auto it = offs.find({k, m});
-                if (it == offs.end()) {
-                    uint32_t off = 0;
-                    MXEC_TRY(encode_coef(*ds.d, k, m, &off));
-                    it = offs.emplace(std::make_pair(k, m), off).first;
-                }
-                groups[m].push_back(RsMixedObject{k, objs[o].shard_size,
-                                                  RsObject{data + dofs[o], &dl[dofs[o]], &stored[pofs[o]],
-                                                           &pl[pofs[o]], it->second, first_bad_dev + pofs[o]}});
-            }
-            return MXEC_OK;
-        }, [&]() -> int {
-            MXEC_HIP(hipMemsetAsync(first_bad_dev, 0xFF, size_t(8 * psum), s));
-            return run_rs_mixed(*ds.d, *ds.slot, s, groups);
-        });
-    });
-}
-
-// ---- locate ------------------------------------------------------------------
-
-static_assert(sizeof(mxec_locate_result) == 24 && sizeof(LocateRec) == sizeof(mxec_locate_result) &&
-                  offsetof(LocateRec, n_bad) == offsetof(mxec_locate_result, n_bad) &&
-                  offsetof(LocateRec, shard_min) == offsetof(mxec_locate_result, shard_min) &&
-                  offsetof(LocateRec, shard_max) == offsetof(mxec_locate_result, shard_max),
-              "the kernel's record is the header's");
-static_assert(kLocateNoShard == MXEC_LOCATE_NO_SHARD, "one sentinel");
-
-namespace {
-// The verify's (k, m) checks, then the locate's own: one parity row cannot
-// tell shards apart, more than eight do not fit one row block.
-int check_km_locate(int k, int m) {
-    MXEC_TRY(check_km(k, m));
-    if (m < 2) return set_error(MXEC_E_INVALID_ARG, "locate needs at least two parity shards");
-    if (m > 8) return set_error(MXEC_E_INVALID_ARG, "locate takes at most eight parity shards");
-    return MXEC_OK;
-}
-}  // namespace
-
-int mxec_locate_outcome(const void* result, uint32_t* shard) {
-    if (!result) return MXEC_LOCATE_MANY;
-    return locate_outcome(static_cast<const mxec_locate_result*>(result), shard);
-}
-
-int mxec_locate(mxec_ctx* ctx, int k, int m, size_t shard_size, const uint8_t* const* data,
-                const size_t* data_len, const uint8_t* const* parity, void* out) {
-    return guarded([&] {
-        MXEC_TRY(check_km_locate(k, m));
-        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-        if (!data || !parity || !out) return set_error(MXEC_E_INVALID_ARG, "null argument");
-        std::vector<uint64_t> len(static_cast<size_t>(k + m), shard_size);
-        for (int j = 0; j < k; ++j) {
-            len[size_t(j)] = data_len ? data_len[j] : shard_size;
-            if (len[size_t(j)] > shard_size)
-                return set_error(MXEC_E_INCORRECT_SHARD_SIZE, "data chunk longer than shard_size");
-            if (len[size_t(j)] && !data[j]) return set_error(MXEC_E_INVALID_ARG, "null data chunk");
-        }
-        for (int i = 0; i < m; ++i)
-            if (!parity[i]) return set_error(MXEC_E_INVALID_ARG, "null parity shard");
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, -1));
-        Slot& slot = *ds.slot;
-        hipStream_t s = slot.stream;
-        // The shards as mxec_verify stages them, then the one record.
-        const uint64_t sa = round_up(shard_size, kSlotAlign);
-        const uint64_t rec_off = sa * uint64_t(k + m);
-        MXEC_TRY(slot.shards.ensure(rec_off + sizeof(LocateRec)));
-        auto* base = static_cast<uint8_t*>(slot.shards.p);
-        auto* rec = reinterpret_cast<LocateRec*>(base + rec_off);
-        std::vector<const uint8_t*> in(static_cast<size_t>(k));
-        std::vector<uint8_t*> stored(static_cast<size_t>(m));
-        std::vector<UploadSeg> up;
-        for (int j = 0; j < k; ++j) {
-            in[size_t(j)] = base + sa * uint64_t(j);
-            if (len[size_t(j)]) up.push_back({sa * uint64_t(j), data[j], len[size_t(j)]});
-        }
-        for (int i = 0; i < m; ++i) {
-            stored[size_t(i)] = base + sa * uint64_t(k + i);
-            up.push_back({sa * uint64_t(k + i), parity[i], shard_size});
-        }
-        MXEC_TRY(upload_segments(slot, s, base, up, copy_waves_get(*ds.d)));
-        uint32_t off = 0;
-        MXEC_TRY(with_stable_coef(
-            *ds.d, s, [&] { return encode_coef(*ds.d, k, m, &off); },
-            [&] {
-                MXEC_HIP(launch_locate_init(rec, 1, s));
-                RsObject ob{in.data(), len.data(), stored.data(), len.data() + k, off, nullptr, rec};
-                return run_rs(*ds.d, slot, s, shard_size, k, m, {ob});
-            }));
-        std::vector<DownloadSeg> down{{rec_off, static_cast<uint8_t*>(out), sizeof(LocateRec)}};
-        return download_segments(slot, s, base, down, false);
-    });
-}
-
-int mxec_locate_strided_device(mxec_ctx* ctx, int dev, void* stream, int k, int m, uint64_t shard_size,
-                               uint64_t n_obj, const uint8_t* data, uint64_t data_obj_stride,
-                               uint64_t data_shard_stride, const uint64_t* data_len, const uint8_t* parity,
-                               uint64_t parity_obj_stride, uint64_t parity_shard_stride, void* out_dev) {
-    return guarded([&] {
-        MXEC_TRY(check_km_locate(k, m));
-        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-        if (n_obj == 0) return MXEC_OK;
-        if (!data || !parity) return set_error(MXEC_E_INVALID_ARG, "null base pointer");
-        if (!out_dev) return set_error(MXEC_E_INVALID_ARG, "null result array");
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, dev));
-        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-        auto* recs = static_cast<LocateRec*>(out_dev);
-        uint32_t off = 0;
-        std::vector<uint64_t> len(static_cast<size_t>(k + m), shard_size);
-        for (int j = 0; j < k; ++j)
-            if (data_len) len[size_t(j)] = std::min<uint64_t>(data_len[j], shard_size);
-        std::vector<const uint8_t*> in(static_cast<size_t>(n_obj * k));
-        std::vector<uint8_t*> stored(static_cast<size_t>(n_obj * m));  // read only
-        std::vector<RsObject> objs(static_cast<size_t>(n_obj));
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            for (int j = 0; j < k; ++j) in[o * k + j] = data + o * data_obj_stride + j * data_shard_stride;
-            for (int i = 0; i < m; ++i)
-                stored[o * m + i] = const_cast<uint8_t*>(parity) + o * parity_obj_stride + i * parity_shard_stride;
-            objs[o] = RsObject{&in[o * k], len.data(), &stored[o * m], len.data() + k, 0, nullptr, recs + o};
-        }
-        return with_stable_coef(
-            *ds.d, s, [&] { return encode_coef(*ds.d, k, m, &off); },
-            [&] {
-                // Initialised inside the launch step: a pass queued again
-                // after a table recycle (with_stable_coef) starts from clean
-                // records, so n_bad counts one pass.
-                MXEC_HIP(launch_locate_init(recs, n_obj, s));
-                for (auto& ob : objs) ob.coef_off = off;
-                return run_rs(*ds.d, *ds.slot, s, shard_size, k, m, objs);
-            });
-    });
-}
-
-int mxec_locate_batch_device(mxec_ctx* ctx, int dev, void* stream, const mxec_object* objs, uint64_t n_obj,
-                             const uint8_t* const* data, const uint64_t* data_len,
-                             const uint8_t* const* parity, void* out_dev) {
-    return guarded([&] {
-        if (n_obj == 0) return MXEC_OK;
-        if (!objs || !data || !parity || !out_dev) return set_error(MXEC_E_INVALID_ARG, "null argument");
-        // Every object's (k, m) before a device is touched.
-        std::vector<uint64_t> dofs(static_cast<size_t>(n_obj)), pofs(static_cast<size_t>(n_obj));
-        uint64_t dsum = 0, psum = 0;
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            MXEC_TRY(check_km_locate(objs[o].k, objs[o].m));
-            if (objs[o].shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-            dofs[o] = dsum;
-            pofs[o] = psum;
-            dsum += uint64_t(objs[o].k);
-            psum += uint64_t(objs[o].m);
-        }
-        std::vector<uint8_t*> stored(static_cast<size_t>(psum));  // read only
-        for (uint64_t i = 0; i < psum; ++i) {
-            if (!parity[i]) return set_error(MXEC_E_INVALID_ARG, "null parity pointer " + std::to_string(i));
-            stored[i] = const_cast<uint8_t*>(parity[i]);
-        }
-        std::vector<uint64_t> dl(static_cast<size_t>(dsum)), pl(static_cast<size_t>(psum));
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            for (int j = 0; j < objs[o].k; ++j) {
-                const uint64_t idx = dofs[o] + uint64_t(j);
-                dl[idx] = data_len ? std::min<uint64_t>(data_len[idx], objs[o].shard_size) : objs[o].shard_size;
-            }
-            for (int i = 0; i < objs[o].m; ++i) pl[pofs[o] + uint64_t(i)] = objs[o].shard_size;
-        }
-        for (uint64_t j = 0; j < dsum; ++j)
-            if (!data[j] && dl[j]) return set_error(MXEC_E_INVALID_ARG, "null data pointer " + std::to_string(j));
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, dev));
-        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-        auto* recs = static_cast<LocateRec*>(out_dev);
-        // One launch per parity count m, as mxec_verify_batch_device.
-        std::map<int, std::vector<RsMixedObject>> groups;
-        return with_stable_coef(*ds.d, s, [&]() -> int {
-            groups.clear();
-            std::map<std::pair<int, int>, uint32_t> offs;
-            for (uint64_t o = 0; o < n_obj; ++o) {
-                const int k = objs[o].k, m = objs[o].m;
-                auto it = offs.find({k, m});
-                if (it == offs.end()) {
-                    uint32_t off = 0;
-                    MXEC_TRY(encode_coef(*ds.d, k, m, &off));
-                    it = offs.emplace(std::make_pair(k, m), off).first;
-                }
-                groups[m].push_back(RsMixedObject{k, objs[o].shard_size,
-                                                  RsObject{data + dofs[o], &dl[dofs[o]], &stored[pofs[o]],
-                                                           &pl[pofs[o]], it->second, nullptr, recs + o}});
-            }
-            return MXEC_OK;
-        }, [&]() -> int {
-            MXEC_HIP(launch_locate_init(recs, n_obj, s));
-            return run_rs_mixed(*ds.d, *ds.slot, s, groups);
-        });
-    });
-}
-
 int mxec_reconstruct_strided_device(mxec_ctx* ctx, int dev, void* stream, int k, int m,
                                     uint64_t shard_size, uint64_t n_obj, uint8_t* shards,
                                     uint64_t obj_stride, uint64_t shard_stride,
@@ -1088,22 +625,7 @@ int mxec_reconstruct_strided_device(mxec_ctx* ctx, int dev, void* stream, int k,
                 // A batch that fills the chip: its own launch on `stream`,
                 // digests compared on the device (the verify kernel compares
                 // message t against expected[idx[t]]), n flags read back.
-                MXEC_TRY(slot.digests.grow(ptrs.size()));
-                auto* ok = static_cast<uint8_t*>(slot.digests.p);
-                const uint32_t* tmo = nullptr;
-                MXEC_TRY(run_sha(*ds.d, slot, s, ptrs, lens, nullptr, expected_sha_dev, ok, &idx, nullptr, 0, &tmo));
-                const size_t fo = (ptrs.size() + 15) & ~size_t(15);
-                MXEC_TRY(slot.hdig.grow(fo + 16));
-                auto* hflag = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(slot.hdig.p) + fo);
-                *hflag = 0;
-                MXEC_HIP(hipMemcpyAsync(slot.hdig.p, ok, ptrs.size(), hipMemcpyDeviceToHost, s));
-                if (tmo) MXEC_HIP(hipMemcpyAsync(hflag, tmo, 4, hipMemcpyDeviceToHost, s));
-                MXEC_TRY(slot_wait(*ds.slot, s));
-                if (*hflag != 0)
-                    return set_error(MXEC_E_DEVICE, "SHA-256 stream kernel: a wave timed out waiting for its predecessor segment");
-                const auto* okh = static_cast<const uint8_t*>(slot.hdig.p);
-                for (size_t t = 0; t < idx.size(); ++t)
-                    if (!okh[t]) present[idx[t]] = 0;
+                MXEC_TRY(verify_digests_device(*ds.d, slot, s, ptrs, lens, idx, expected_sha_dev, present));
             } else if (!ptrs.empty()) {
                 // A small batch: hashed by the device's combiner together with
                 // every concurrent caller's verification (combiner.cpp), once
@@ -1160,17 +682,7 @@ int mxec_reconstruct_strided_device(mxec_ctx* ctx, int dev, void* stream, int k,
             }
         }
         if (!rebuilt) MXEC_TRY(rebuild(all));
-        int first_err = MXEC_OK;
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            if (status_out) status_out[o] = st[o];
-            if (st[o] != MXEC_OK && first_err == MXEC_OK) {
-                int np = 0;
-                for (int i = 0; i < total; ++i) np += present[o * total + i] != 0;
-                first_err = st[o];
-                set_error(first_err, too_few_msg(np, k, total));
-            }
-        }
-        return first_err;
+        return batch_status(bo, st, status_out);
     });
 }
 
@@ -1221,41 +733,14 @@ int mxec_reconstruct_batch_device(mxec_ctx* ctx, int dev, void* stream, const mx
                     lens.push_back(len[g]);
                     idx.push_back(g);
                 }
-            if (!ptrs.empty()) {
-                MXEC_TRY(slot.digests.grow(ptrs.size()));
-                auto* ok = static_cast<uint8_t*>(slot.digests.p);
-                const uint32_t* tmo = nullptr;
-                MXEC_TRY(run_sha(*ds.d, slot, s, ptrs, lens, nullptr, expected_sha_dev, ok, &idx, nullptr, 0, &tmo));
-                const size_t fo = (ptrs.size() + 15) & ~size_t(15);
-                MXEC_TRY(slot.hdig.grow(fo + 16));
-                auto* hflag = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(slot.hdig.p) + fo);
-                *hflag = 0;
-                MXEC_HIP(hipMemcpyAsync(slot.hdig.p, ok, ptrs.size(), hipMemcpyDeviceToHost, s));
-                if (tmo) MXEC_HIP(hipMemcpyAsync(hflag, tmo, 4, hipMemcpyDeviceToHost, s));
-                MXEC_TRY(slot_wait(slot, s));
-                if (*hflag != 0)
-                    return set_error(MXEC_E_DEVICE, "SHA-256 stream kernel: a wave timed out waiting for its predecessor segment");
-                const auto* okh = static_cast<const uint8_t*>(slot.hdig.p);
-                for (size_t t = 0; t < idx.size(); ++t)
-                    if (!okh[t]) present[idx[t]] = 0;
-            }
+            if (!ptrs.empty())
+                MXEC_TRY(verify_digests_device(*ds.d, slot, s, ptrs, lens, idx, expected_sha_dev, present));
         }
         std::vector<int32_t> st(static_cast<size_t>(n_obj), MXEC_OK);
         std::vector<uint64_t> all(static_cast<size_t>(n_obj));
         for (uint64_t o = 0; o < n_obj; ++o) all[o] = o;
         MXEC_TRY(rebuild_batch(*ds.d, slot, s, (flags & MXEC_F_DATA_ONLY) != 0, bo, all, st));
-        int first_err = MXEC_OK;
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            if (status_out) status_out[o] = st[o];
-            if (st[o] != MXEC_OK && first_err == MXEC_OK) {
-                const int total = objs[o].k + objs[o].m;
-                int np = 0;
-                for (int i = 0; i < total; ++i) np += present[first[o] + uint64_t(i)] != 0;
-                first_err = st[o];
-                set_error(first_err, too_few_msg(np, objs[o].k, total));
-            }
-        }
-        return first_err;
+        return batch_status(bo, st, status_out);
     });
 }
 

@@ -1,6 +1,7 @@
 // ops.hpp — device-pointer level operations shared by every C entry point.
 #pragma once
 
+#include <chrono>
 #include <cstdint>
 #include <exception>
 #include <mutex>
@@ -182,6 +183,20 @@ struct DevScope {
     }
 };
 
+
+// MXEC_PIPE_COPY (knobs.hpp): whether a host-pointer call's copies of
+// mxec_host_alloc memory may go by CU-wave copy kernels -- the reconstruct /
+// hash (GET) paths under auto and waves, the encode (PUT) path under waves
+// only (copy_watch.hpp has the measurements behind the split).
+inline bool copy_waves_get(const Device& d) {
+    if (!d.kn) return false;
+    if (d.kn->pipe_copy == 1) return true;
+    if (d.kn->pipe_copy != 2) return false;
+    const int64_t now = std::chrono::duration_cast<std::chrono::nanoseconds>(
+                            std::chrono::steady_clock::now().time_since_epoch()).count();
+    return now < d.waves_up_until_ns.load() || now < d.waves_down_until_ns.load();
+}
+inline bool copy_waves_put(const Device& d) { return d.kn && d.kn->pipe_copy == 1; }
 
 // PUT body digests of device-resident bodies into mxec_body_sums records
 // (sums.cpp); enqueued on s.

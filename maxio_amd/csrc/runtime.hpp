@@ -307,7 +307,7 @@ struct Device {
     // before these instants copy mxec_host_alloc memory by waves, uploads /
     // downloads.  Only a measured slow bracket sets one, and it lapses on its
     // own: the single-request calls read the same instants
-    // (capi.cpp copy_waves_get).
+    // (ops.hpp copy_waves_get).
     std::atomic<int64_t> waves_up_until_ns{0}, waves_down_until_ns{0};
     // Until this instant a lone speculating verified GET wave downloads by
     // waves (copy_watch.hpp spec_judge).

@@ -673,44 +673,104 @@ int replace_file(const fs::path& dir, const std::string& name, const uint8_t* da
     return MXEC_OK;
 }
 
+// One object's shards in memory, as the scrub and the locate pass need them.
+struct ObjectShards {
+    Manifest man;
+    int k = 0, m = 0, total = 0;
+    uint64_t shard = 0;
+    std::vector<Bytes> bufs;
+    std::vector<uint8_t*> ptrs;
+    std::vector<size_t> lens;
+
+    // The manifest and its geometry, checked as ReedSolomon::new would.
+    int open(const fs::path& dir) {
+        MXEC_TRY(read_manifest(dir, man));
+        k = int(man.chunk_count);
+        m = man.has_parity ? int(man.parity_shards) : 0;
+        shard = man.has_shard ? man.shard_size : man.chunk_size;
+        if (m > 0) {  // an object without parity has nothing ReedSolomon::new would see
+            const int rc = mxec_rs_check(k, m);
+            if (rc) return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
+        }
+        total = k + m;
+        if (int(man.chunks.size()) < total) return set_error(MXEC_E_JSON, "JSON error: manifest lists fewer shards than k+m");
+        return MXEC_OK;
+    }
+
+    // The shard files, parity included, read and sized as reconstruct_from_dir
+    // does; returns whether each is there at its size.  With `state` (total
+    // entries) all are read, a missing or wrong-sized one noted there and
+    // zero-filled where a heal rebuilds it; without, the first such ends it.
+    bool load(const fs::path& dir, uint8_t* state) {
+        bufs.resize(size_t(total));
+        ptrs.resize(size_t(total));
+        lens.resize(size_t(total));
+        bool whole = true;
+        for (int i = 0; i < total && (whole || state); ++i) {
+            const size_t want = size_t(i < k ? std::min<uint64_t>(man.chunks[size_t(i)].size, shard) : shard);
+            Bytes& b = bufs[size_t(i)];
+            const bool there = read_file(dir / chunk_name(uint32_t(i)), b) == MXEC_OK;
+            whole = whole && there && b.size() == want;
+            if (state && !(there && b.size() == want)) {
+                state[i] = there ? MXEC_SHARD_BAD_SIZE : MXEC_SHARD_MISSING;
+                b.assign(want, 0);
+            }
+            lens[size_t(i)] = want;
+            ptrs[size_t(i)] = b.data();
+        }
+        set_error(0, "");  // a missing file is a finding, not this call's error
+        return whole;
+    }
+};
+
+// The heal: shards `bad` rebuilt from all the others as they are (the decode
+// checks no digest) and hashed; only if each is what the manifest recorded
+// (expected: total x 32 bytes, parsed: which of them parsed) are they written
+// under their final names.  *wrote: files replaced, all of `bad` or none.
+int rebuild_and_replace(mxec_ctx* ctx, const fs::path& dir, ObjectShards& ob, const std::vector<int>& bad,
+                        const std::vector<uint8_t>& expected, const std::vector<uint8_t>& parsed, size_t* wrote) {
+    *wrote = 0;
+    std::vector<uint8_t> present(static_cast<size_t>(ob.total), 1);
+    for (int i : bad) {
+        present[size_t(i)] = 0;
+        ob.bufs[size_t(i)].assign(ob.lens[size_t(i)], 0);
+        ob.ptrs[size_t(i)] = ob.bufs[size_t(i)].data();
+    }
+    // A zero-length shard has no buffer of its own; the decode wants a pointer.
+    uint8_t none = 0;
+    for (auto& p : ob.ptrs)
+        if (!p) p = &none;
+    int np = 0;
+    MXEC_TRY(mxec_reconstruct(ctx, ob.k, ob.m, ob.shard, ob.ptrs.data(), ob.lens.data(), nullptr, present.data(), 0, &np));
+    std::vector<const uint8_t*> hp;
+    std::vector<size_t> hl;
+    for (int i : bad) { hp.push_back(ob.ptrs[size_t(i)]); hl.push_back(ob.lens[size_t(i)]); }
+    std::vector<uint8_t> dig(hp.size() * 32);
+    MXEC_TRY(mxec_sha256_batch(ctx, hp.data(), hl.data(), hp.size(), reinterpret_cast<uint8_t(*)[32]>(dig.data())));
+    for (size_t t = 0; t < bad.size(); ++t)
+        if (!parsed[size_t(bad[t])] || std::memcmp(&dig[t * 32], &expected[size_t(bad[t]) * 32], 32) != 0)
+            return MXEC_OK;  // more is wrong than the shards named
+    for (size_t t = 0; t < bad.size(); ++t, ++*wrote)
+        MXEC_TRY(replace_file(dir, chunk_name(uint32_t(bad[t])), hp[t], hl[t]));
+    return MXEC_OK;
+}
+
 int scrub_object(mxec_ctx* ctx, const fs::path& dir, uint32_t flags, mxec_scrub_report* rep) {
     if (flags & MXEC_SCRUB_HEAL) flags |= MXEC_SCRUB_DIGESTS;
-    Manifest man;
-    MXEC_TRY(read_manifest(dir, man));
-    const int k = int(man.chunk_count);
-    const int m = man.has_parity ? int(man.parity_shards) : 0;
-    const uint64_t shard = man.has_shard ? man.shard_size : man.chunk_size;
-    if (m > 0) {  // an object without parity has nothing ReedSolomon::new would see
-        const int rc = mxec_rs_check(k, m);
-        if (rc) return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
-    }
-    const int total = k + m;
+    ObjectShards ob;
+    MXEC_TRY(ob.open(dir));
+    const int k = ob.k, m = ob.m, total = ob.total;
     if (total > int(sizeof rep->shard_state))
         return set_error(MXEC_E_INVALID_ARG, "scrub: more shards than the report holds (" + std::to_string(total) + ")");
-    if (int(man.chunks.size()) < total) return set_error(MXEC_E_JSON, "JSON error: manifest lists fewer shards than k+m");
     rep->k = uint32_t(k);
     rep->m = uint32_t(m);
-
-    // Every shard file, parity included, read and sized as reconstruct_from_dir does.
-    std::vector<Bytes> bufs(static_cast<size_t>(total));
-    std::vector<uint8_t*> ptrs(static_cast<size_t>(total));
-    std::vector<size_t> lens(static_cast<size_t>(total));
     uint8_t* st = rep->shard_state;
-    for (int i = 0; i < total; ++i) {
-        const size_t want = size_t(i < k ? std::min<uint64_t>(man.chunks[size_t(i)].size, shard) : shard);
-        Bytes& b = bufs[size_t(i)];
-        if (read_file(dir / chunk_name(uint32_t(i)), b) != MXEC_OK) st[i] = MXEC_SHARD_MISSING;
-        else if (b.size() != want) st[i] = MXEC_SHARD_BAD_SIZE;
-        if (st[i] != MXEC_SHARD_OK) b.assign(want, 0);  // where a heal rebuilds it
-        lens[size_t(i)] = want;
-        ptrs[size_t(i)] = b.data();
-    }
-    set_error(0, "");  // a missing file is a finding, not this call's error
+    const bool whole = ob.load(dir, st);
 
-    if ((flags & MXEC_SCRUB_PARITY) && m > 0 && mxec::scrub_damaged(st, uint32_t(total)) == 0) {
+    if ((flags & MXEC_SCRUB_PARITY) && m > 0 && whole) {
         std::vector<uint64_t> fb(static_cast<size_t>(m));
         int ok = 0;
-        MXEC_TRY(mxec_verify(ctx, k, m, shard, ptrs.data(), lens.data(), ptrs.data() + k, fb.data(), &ok));
+        MXEC_TRY(mxec_verify(ctx, k, m, ob.shard, ob.ptrs.data(), ob.lens.data(), ob.ptrs.data() + k, fb.data(), &ok));
         rep->parity_consistent = ok;
         for (uint64_t v : fb) rep->parity_first_bad = std::min(rep->parity_first_bad, v);
     }
@@ -722,14 +782,14 @@ int scrub_object(mxec_ctx* ctx, const fs::path& dir, uint32_t flags, mxec_scrub_
         std::vector<size_t> hl;
         std::vector<int> hi;
         for (int i = 0; i < total; ++i) {
-            parsed[size_t(i)] = unhex32(man.chunks[size_t(i)].sha256, &expected[size_t(i) * 32]);
+            parsed[size_t(i)] = unhex32(ob.man.chunks[size_t(i)].sha256, &expected[size_t(i) * 32]);
             if (st[i] != MXEC_SHARD_OK) continue;
             if (!parsed[size_t(i)]) {  // a digest that does not parse can never match
                 st[i] = MXEC_SHARD_BAD_DIGEST;
                 continue;
             }
-            hp.push_back(lens[size_t(i)] ? ptrs[size_t(i)] : reinterpret_cast<const uint8_t*>(""));
-            hl.push_back(lens[size_t(i)]);
+            hp.push_back(ob.lens[size_t(i)] ? ob.ptrs[size_t(i)] : reinterpret_cast<const uint8_t*>(""));
+            hl.push_back(ob.lens[size_t(i)]);
             hi.push_back(i);
         }
         std::vector<uint8_t> dig(hp.size() * 32);
@@ -741,44 +801,16 @@ int scrub_object(mxec_ctx* ctx, const fs::path& dir, uint32_t flags, mxec_scrub_
     rep->n_damaged = mxec::scrub_damaged(st, uint32_t(total));
     bool rebuilt_ok = false;
     if ((flags & MXEC_SCRUB_HEAL) && mxec::scrub_can_heal(rep->n_damaged, uint32_t(m))) {
-        // Every damaged shard, data and parity, from the verified ones (the
-        // digests were checked above, so the decode takes the mask as it is).
-        std::vector<uint8_t> present(static_cast<size_t>(total));
+        // Every damaged shard, data and parity, from the verified ones.
         std::vector<int> bad;
-        for (int i = 0; i < total; ++i) {
-            present[size_t(i)] = st[i] == MXEC_SHARD_OK;
-            if (!present[size_t(i)]) {
-                bad.push_back(i);
-                bufs[size_t(i)].assign(lens[size_t(i)], 0);
-                ptrs[size_t(i)] = bufs[size_t(i)].data();
-            }
-        }
-        // A zero-length shard has no buffer of its own; the decode wants a pointer.
-        uint8_t none = 0;
         for (int i = 0; i < total; ++i)
-            if (!ptrs[size_t(i)]) ptrs[size_t(i)] = &none;
-        int np = 0;
-        MXEC_TRY(mxec_reconstruct(ctx, k, m, shard, ptrs.data(), lens.data(), nullptr, present.data(), 0, &np));
-        // Written only if every rebuilt shard is what the manifest recorded.
-        std::vector<const uint8_t*> hp;
-        std::vector<size_t> hl;
-        for (int i : bad) {
-            hp.push_back(ptrs[size_t(i)]);
-            hl.push_back(lens[size_t(i)]);
-        }
-        std::vector<uint8_t> dig(hp.size() * 32);
-        MXEC_TRY(mxec_sha256_batch(ctx, hp.data(), hl.data(), hp.size(), reinterpret_cast<uint8_t(*)[32]>(dig.data())));
-        rebuilt_ok = true;
-        for (size_t t = 0; t < bad.size(); ++t)
-            rebuilt_ok = rebuilt_ok && parsed[size_t(bad[t])] &&
-                         std::memcmp(&dig[t * 32], &expected[size_t(bad[t]) * 32], 32) == 0;
-        if (rebuilt_ok) {
-            for (int i : bad) {
-                MXEC_TRY(replace_file(dir, chunk_name(uint32_t(i)), ptrs[size_t(i)], lens[size_t(i)]));
-                st[i] |= MXEC_SHARD_HEALED;
-                ++rep->n_healed;
-            }
-        }
+            if (st[i] != MXEC_SHARD_OK) bad.push_back(i);
+        size_t wrote = 0;
+        const int rc = rebuild_and_replace(ctx, dir, ob, bad, expected, parsed, &wrote);
+        for (size_t t = 0; t < wrote; ++t) st[bad[t]] |= MXEC_SHARD_HEALED;
+        rep->n_healed += uint32_t(wrote);
+        MXEC_TRY(rc);
+        rebuilt_ok = wrote == bad.size();
     }
     rep->verdict = mxec::scrub_verdict(rep->n_damaged, uint32_t(m), rep->parity_consistent,
                                        (flags & MXEC_SCRUB_HEAL) != 0, rebuilt_ok);
@@ -807,66 +839,30 @@ namespace {
 // The scrub's parity pass, naming the shard: no digest of any present shard.
 // A heal rebuilds the one located shard and hashes that alone.
 int locate_object(mxec_ctx* ctx, const fs::path& dir, uint32_t flags, mxec_locate_report* rep) {
-    Manifest man;
-    MXEC_TRY(read_manifest(dir, man));
-    const int k = int(man.chunk_count);
-    const int m = man.has_parity ? int(man.parity_shards) : 0;
-    const uint64_t shard = man.has_shard ? man.shard_size : man.chunk_size;
-    if (m > 0) {
-        const int rc = mxec_rs_check(k, m);
-        if (rc) return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
-    }
-    const int total = k + m;
-    if (int(man.chunks.size()) < total) return set_error(MXEC_E_JSON, "JSON error: manifest lists fewer shards than k+m");
-    rep->k = uint32_t(k);
-    rep->m = uint32_t(m);
+    ObjectShards ob;
+    MXEC_TRY(ob.open(dir));
+    rep->k = uint32_t(ob.k);
+    rep->m = uint32_t(ob.m);
     rep->outcome = MXEC_LOCATE_SKIPPED;
-    if (m < 2 || m > 8) return MXEC_OK;
-
-    // Every shard file read and sized as scrub_object does; one that is
-    // missing or wrong-sized is the digest pass's to report.
-    std::vector<Bytes> bufs(static_cast<size_t>(total));
-    std::vector<uint8_t*> ptrs(static_cast<size_t>(total));
-    std::vector<size_t> lens(static_cast<size_t>(total));
-    bool whole = true;
-    for (int i = 0; i < total && whole; ++i) {
-        const size_t want = size_t(i < k ? std::min<uint64_t>(man.chunks[size_t(i)].size, shard) : shard);
-        Bytes& b = bufs[size_t(i)];
-        whole = read_file(dir / chunk_name(uint32_t(i)), b) == MXEC_OK && b.size() == want;
-        lens[size_t(i)] = want;
-        ptrs[size_t(i)] = b.data();
-    }
-    set_error(0, "");  // a missing file is a finding, not this call's error
-    if (!whole) return MXEC_OK;
+    if (ob.m < 2 || ob.m > 8) return MXEC_OK;
+    // A shard that is missing or wrong-sized is the digest pass's to report.
+    if (!ob.load(dir, nullptr)) return MXEC_OK;
 
     mxec_locate_result res;
-    MXEC_TRY(mxec_locate(ctx, k, m, shard, ptrs.data(), lens.data(), ptrs.data() + k, &res));
+    MXEC_TRY(mxec_locate(ctx, ob.k, ob.m, ob.shard, ob.ptrs.data(), ob.lens.data(), ob.ptrs.data() + ob.k, &res));
     rep->first_bad = res.first_bad;
     rep->n_bad = res.n_bad;
     rep->outcome = uint32_t(mxec_locate_outcome(&res, &rep->shard));
     if (!(flags & MXEC_LOCATE_F_HEAL) || rep->outcome != MXEC_LOCATE_ONE) return MXEC_OK;
+    if (rep->shard >= uint32_t(ob.total)) return MXEC_OK;
 
-    const int bad = int(rep->shard);
-    if (bad >= total) return MXEC_OK;
-    uint8_t expected[32];
-    if (!unhex32(man.chunks[size_t(bad)].sha256, expected)) return MXEC_OK;  // nothing to check a rebuild against
-    std::vector<uint8_t> present(static_cast<size_t>(total), 1);
-    present[size_t(bad)] = 0;
-    bufs[size_t(bad)].assign(lens[size_t(bad)], 0);
-    ptrs[size_t(bad)] = bufs[size_t(bad)].data();
-    // A zero-length shard has no buffer of its own; the decode wants a pointer.
-    uint8_t none = 0;
-    for (int i = 0; i < total; ++i)
-        if (!ptrs[size_t(i)]) ptrs[size_t(i)] = &none;
-    int np = 0;
-    MXEC_TRY(mxec_reconstruct(ctx, k, m, shard, ptrs.data(), lens.data(), nullptr, present.data(), 0, &np));
-    const uint8_t* hp = ptrs[size_t(bad)];
-    const size_t hl = lens[size_t(bad)];
-    uint8_t dig[32];
-    MXEC_TRY(mxec_sha256_batch(ctx, &hp, &hl, 1, reinterpret_cast<uint8_t(*)[32]>(dig)));
-    if (std::memcmp(dig, expected, 32) != 0) return MXEC_OK;  // more is wrong than one shard: the scrub's heal
-    MXEC_TRY(replace_file(dir, chunk_name(uint32_t(bad)), hp, hl));
-    rep->healed = 1;
+    const std::vector<int> bad{int(rep->shard)};
+    std::vector<uint8_t> expected(size_t(ob.total) * 32, 0), parsed(static_cast<size_t>(ob.total), 0);
+    parsed[rep->shard] = unhex32(ob.man.chunks[rep->shard].sha256, &expected[size_t(rep->shard) * 32]);
+    if (!parsed[rep->shard]) return MXEC_OK;  // nothing to check a rebuild against
+    size_t wrote = 0;  // 0 when more is wrong than one shard: the scrub's heal
+    MXEC_TRY(rebuild_and_replace(ctx, dir, ob, bad, expected, parsed, &wrote));
+    rep->healed = wrote == 1;
     return MXEC_OK;
 }
 

@@ -139,6 +139,24 @@ def _u64p(vals: Sequence[int]):
     return (ctypes.c_uint64 * max(1, len(vals)))(*vals)
 
 
+def _batch_args(objs, data_ptrs, parity_ptrs, data_len):
+    """A *_batch_device call's leading arguments (ctypes arrays pass through as built)."""
+    arr = objs if isinstance(objs, ctypes.Array) else (N.Object * len(objs))(*[N.Object(k, m, s) for (k, m, s) in objs])
+    dp = data_ptrs if isinstance(data_ptrs, ctypes.Array) else _pp(data_ptrs)
+    pp = parity_ptrs if isinstance(parity_ptrs, ctypes.Array) else _pp(parity_ptrs)
+    dl = None if data_len is None else (data_len if isinstance(data_len, ctypes.Array) else _u64p(data_len))
+    return arr, dp, pp, dl
+
+
+def _data_and_parity(data: Sequence, parity: Sequence, shard_size: int):
+    """uint8 views of a verify / locate call's shards, the parity all shard_size bytes."""
+    par = [_u8(p) for p in parity]
+    for p in par:
+        if p.size != shard_size:
+            raise RSError(-9, "parity shard is not shard_size bytes")
+    return [_u8(d) for d in data], par
+
+
 def rs_check(k: int, m: int) -> None:
     """ReedSolomon::new(k, m) argument checks (no GPU needed)."""
     _check(N.lib().mxec_rs_check(k, m))
@@ -314,11 +332,7 @@ class Context:
         first_bad) -- per parity row the lowest byte offset at which the
         stored row differs from the recomputed one, VERIFY_OK where they
         agree.  Data chunks shorter than shard_size count as zero padded."""
-        arrs = [_u8(d) for d in data]
-        par = [_u8(p) for p in parity]
-        for p in par:
-            if p.size != shard_size:
-                raise RSError(-9, "parity shard is not shard_size bytes")
+        arrs, par = _data_and_parity(data, parity, shard_size)
         k, m = len(arrs), len(par)
         fb = np.zeros(max(1, m), np.uint64)
         ok = ctypes.c_int(0)
@@ -332,11 +346,7 @@ class Context:
         <= 8).  Returns first_bad, n_bad, shard_min, shard_max as the kernel
         left them, plus outcome (LOCATE_CLEAN / _ONE / _MANY) and shard (the
         damaged shard's index when ONE, else None)."""
-        arrs = [_u8(d) for d in data]
-        par = [_u8(p) for p in parity]
-        for p in par:
-            if p.size != shard_size:
-                raise RSError(-9, "parity shard is not shard_size bytes")
+        arrs, par = _data_and_parity(data, parity, shard_size)
         r = N.LocateResult()
         _check(self._lib.mxec_locate(
             self._h, len(arrs), len(par), shard_size, _pp([_ptr(a) for a in arrs]), _szp([a.size for a in arrs]),
@@ -449,12 +459,8 @@ class Context:
 
     def encode_batch_device(self, objs: Sequence[tuple], data_ptrs, parity_ptrs, data_len=None,
                             digests_ptr=None, dev=0, stream=None):
-        """Objects of mixed (k, m, shard_size); one launch per m (ctypes
-        arrays for objs / pointers / lengths pass through as built)."""
-        arr = objs if isinstance(objs, ctypes.Array) else (N.Object * len(objs))(*[N.Object(k, m, s) for (k, m, s) in objs])
-        dp = data_ptrs if isinstance(data_ptrs, ctypes.Array) else _pp(data_ptrs)
-        pp = parity_ptrs if isinstance(parity_ptrs, ctypes.Array) else _pp(parity_ptrs)
-        dl = None if data_len is None else (data_len if isinstance(data_len, ctypes.Array) else _u64p(data_len))
+        """Objects of mixed (k, m, shard_size); one launch per m."""
+        arr, dp, pp, dl = _batch_args(objs, data_ptrs, parity_ptrs, data_len)
         _check(self._lib.mxec_encode_batch_device(self._h, dev, stream, arr, len(objs), dp, dl, pp, digests_ptr))
 
     def verify_strided_device(self, k, m, shard_size, n_obj, data_ptr, data_obj_stride,
@@ -471,10 +477,7 @@ class Context:
                             dev=0, stream=None):
         """mxec_verify_batch_device: objects of mixed (k, m, shard_size), one
         launch per m; first_bad_ptr is a device array of sum(m) uint64."""
-        arr = objs if isinstance(objs, ctypes.Array) else (N.Object * len(objs))(*[N.Object(k, m, s) for (k, m, s) in objs])
-        dp = data_ptrs if isinstance(data_ptrs, ctypes.Array) else _pp(data_ptrs)
-        pp = parity_ptrs if isinstance(parity_ptrs, ctypes.Array) else _pp(parity_ptrs)
-        dl = None if data_len is None else (data_len if isinstance(data_len, ctypes.Array) else _u64p(data_len))
+        arr, dp, pp, dl = _batch_args(objs, data_ptrs, parity_ptrs, data_len)
         _check(self._lib.mxec_verify_batch_device(self._h, dev, stream, arr, len(objs), dp, dl, pp, first_bad_ptr))
 
     def locate_strided_device(self, k, m, shard_size, n_obj, data_ptr, data_obj_stride,
@@ -492,10 +495,7 @@ class Context:
                             dev=0, stream=None):
         """mxec_locate_batch_device: objects of mixed (k, m, shard_size), one
         launch per m; out_ptr is a device array of len(objs) records."""
-        arr = objs if isinstance(objs, ctypes.Array) else (N.Object * len(objs))(*[N.Object(k, m, s) for (k, m, s) in objs])
-        dp = data_ptrs if isinstance(data_ptrs, ctypes.Array) else _pp(data_ptrs)
-        pp = parity_ptrs if isinstance(parity_ptrs, ctypes.Array) else _pp(parity_ptrs)
-        dl = None if data_len is None else (data_len if isinstance(data_len, ctypes.Array) else _u64p(data_len))
+        arr, dp, pp, dl = _batch_args(objs, data_ptrs, parity_ptrs, data_len)
         _check(self._lib.mxec_locate_batch_device(self._h, dev, stream, arr, len(objs), dp, dl, pp, out_ptr))
 
     def encode_batch_host(self, objs: Sequence[tuple], data_ptrs, parity_ptrs, data_len=None,

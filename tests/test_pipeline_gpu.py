@@ -477,7 +477,7 @@ def test_single_request_calls_on_host_alloc_buffers(ctx_with, copy):
 def test_single_request_calls_follow_the_verdict(floor, waves):
     """under MXEC_PIPE_COPY=auto the single-request hash call
     copies mxec_host_alloc buffers by waves exactly while a measured slow
-    bracket's hold lasts (capi.cpp copy_waves_get reads the holds).  An
+    bracket's hold lasts (ops.hpp copy_waves_get reads the holds).  An
     RS-only host GET with an unreachable floor is judged slow (its upload
     and download brackets); a mxec_sha256_batch issued right after it --
     well inside the 1-2 s holds -- moves its buffers by waves (wave_blocks
