@@ -86,15 +86,11 @@ constexpr uint32_t kMultiR = 4;
 // n records to the clean pattern {~0, 0, ~0, 0}.
 hipError_t launch_locate_init(LocateRec* recs, uint64_t n, hipStream_t s);
 
-// Tuning knobs of the interior kernel (tools/kernel_lab.cpp sweeps them).
+// Geometry of a launch of the interior kernel (tools/kernel_lab.cpp sweeps
+// the grid).
 struct RsVariant {
-    int vecs = 2;           // 16-byte column vectors per lane per tile (1, 2, 4)
-    bool nt = false;        // nontemporal loads / stores
+    int vecs = 2;           // 16-byte column vectors per lane per tile: 4 for r_total <= 4, else 2
     int blocks_per_cu = 8;  // grid = n_cus * blocks_per_cu (grid-stride)
-    int min_waves = 0;      // 3: compile for >= 3 waves per SIMD (<= 168 VGPRs; V = 4, nt)
-    bool load_nt = true;    // with nt: false = plain loads, nontemporal stores (V = 4, R <= 4; lab)
-    bool store_nt = true;   // with nt: false = nontemporal loads, plain stores (V = 4, R <= 4; lab)
-    int group = 4;          // inputs loaded per step; 8 with V = 2, R = 3..4 (lab)
 };
 
 // Uniform launches, or grouped ones (a.tiles set: rs_group_variant, aligned).
@@ -108,7 +104,7 @@ uint64_t rs_tile_bytes(const RsVariant& v);
 
 // SHA-256 over n messages, one lane per message.  If `expected` is set the
 // kernel also writes ok[i] = (digest == expected[i]).
-// Piece mode of the quad forms (the host pipeline hashes every chunk piece by
+// Piece mode of the lag pair form (the host pipeline hashes every chunk piece by
 // piece while later pieces still upload): launch message i is the next piece
 // of the chain kept in state slot slot[i].  With resume the chain continues
 // from state[slot] (else from the IV).  total[i] == kShaNotFinal: the piece
@@ -117,6 +113,15 @@ uint64_t rs_tile_bytes(const RsVariant& v);
 // padded and finished into digests[slot] (ok[slot] against
 // expected[exp_idx ? exp_idx[slot] : slot]).
 constexpr uint64_t kShaNotFinal = ~uint64_t(0);
+// The kernel forms (ShaArgs::force, Knobs::sha_form).  4 and 5 were the
+// same-round and one-message lag quad forms (removed; DESIGN_HISTORY.md).
+enum ShaForm : int {
+    kShaAuto = 0,     // by message count (launch_sha256)
+    kShaOneWave = 1,  // one wave per 64 messages
+    kShaSplit = 2,    // producer / consumer waves, one lane per message
+    kShaStream = 3,   // persistent waves over (group, segment) items
+    kShaLagPair = 6,  // two lanes per message, the a-side two rounds behind
+};
 struct ShaPiece {
     uint32_t* state = nullptr;        // [slots][8] (a..h); null: whole messages
     const uint32_t* slot = nullptr;   // [n]
@@ -133,9 +138,7 @@ struct ShaArgs {
                                  //   (null: expected[i])
     uint8_t* ok;                 // [n] or null
     uint32_t n;
-    int force = 0;               // 0 auto, 1 one wave per 64 messages, 2 split,
-                                 // 3 stream (needs the fields below), 4 quad,
-                                 // 5 lag quad
+    int force = kShaAuto;        // a ShaForm (kShaStream needs the fields below)
     uint32_t n_cus = 0;          // the device's CUs (auto form choice; 0: 256)
     // Stream form (batches of more 64-message groups than the chip has
     // SIMDs): persistent waves take (group, segment) items in segment-major
@@ -147,12 +150,10 @@ struct ShaArgs {
     uint32_t waves = 0;          // persistent waves
     uint32_t wg_waves = 1;       // waves per workgroup (1 or 4; waves divisible by it)
     uint32_t seg_max = 0;        // segments of the longest message
-    ShaPiece piece;              // piece mode (quad forms, force 4 or 5 only)
+    ShaPiece piece;              // piece mode (kShaLagPair, or auto within its size)
 };
-// Messages per workgroup of the quad form (three consumer waves of 16).
-constexpr uint32_t kShaQuadMsgs = 48;
-// Messages per workgroup of the lag quad form with two messages per quad
-// (two consumer waves of 32): the auto latency form, one workgroup per CU.
+// Messages per workgroup of the lag pair form (two consumer waves of 32, two
+// lanes per message): the auto latency form, one workgroup per CU.
 constexpr uint32_t kShaLagMsgs = 64;
 // A chain's pace per 64-byte block on the MI355X (us), for host-side
 // estimates of a launch's length (combiner.cpp): the lag pair form the auto

@@ -2,6 +2,8 @@
 // environment (called by mxec_open).
 #include "knobs.hpp"
 
+#include "kernels.hpp"
+
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -80,7 +82,7 @@ Knobs read_knobs() {
     k.rs_multi = env_flag("MXEC_RS_MULTI", true);
     {
         static const char* const forms[] = {"auto", "one", "split", "stream", "lagpair", nullptr};
-        static const int form_id[] = {0, 1, 2, 3, 6};
+        static const int form_id[] = {kShaAuto, kShaOneWave, kShaSplit, kShaStream, kShaLagPair};
         const int f = env_choice("MXEC_SHA_FORM", forms, "auto");
         if (f >= 0) k.sha_form = form_id[f];
     }

@@ -24,7 +24,7 @@ struct Knobs {
     bool spin_wait = false;        // MXEC_SPIN_WAIT: host waits spin instead of sleeping
     bool rs_tune = true;           // MXEC_RS_TUNE: online grid choice for large uniform RS launches
     bool rs_multi = true;          // MXEC_RS_MULTI: mixed-r batches as one multi-r launch
-    int sha_form = 0;              // MXEC_SHA_FORM: 0 auto, 1 one, 2 split, 3 stream, 6 lagpair
+    int sha_form = 0;              // MXEC_SHA_FORM: a ShaForm (kernels.hpp), 0 = auto
     int desc_upload = 1;           // MXEC_DESC_UPLOAD: 0 inline, 1 auto, 2 side stream
     uint64_t pipe_piece = uint64_t(1) << 20;  // MXEC_PIPE_PIECE_MB (0: whole chunks)
     bool pipe_piece_auto = true;   // MXEC_PIPE_PIECE_MB unset: 1, 2 or 4 MiB per wave (pipeline.hpp)

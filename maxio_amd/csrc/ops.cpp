@@ -607,11 +607,11 @@ int run_sha(Device& dev, Slot& slot, hipStream_t s, const std::vector<const uint
     bool stream = false;
     if (!items_fit) {
         // many messages plus one very long one: the split / one-wave forms
-    } else if (tmo_dev && !arena && (form == 0 || form == 3) && n < (uint64_t(1) << 31)) {
+    } else if (tmo_dev && !arena && (form == kShaAuto || form == kShaStream) && n < (uint64_t(1) << 31)) {
         bool aligned = true;
         for (const uint8_t* p : ptrs) aligned = aligned && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-        stream = aligned && (sha_stream_size(groups, simds) || form == 3 || env_form == 3);
-    } else if (tmo_dev && !arena && env_form == 3 && n < (uint64_t(1) << 31)) {
+        stream = aligned && (sha_stream_size(groups, simds) || form == kShaStream || env_form == kShaStream);
+    } else if (tmo_dev && !arena && env_form == kShaStream && n < (uint64_t(1) << 31)) {
         bool aligned = true;
         for (const uint8_t* p : ptrs) aligned = aligned && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
         stream = aligned;
@@ -637,12 +637,13 @@ int run_sha(Device& dev, Slot& slot, hipStream_t s, const std::vector<const uint
     a.ok = ok_dev;
     a.n = uint32_t(n);
     a.n_cus = uint32_t(dev.n_cus);
-    a.force = form == 3 && !stream ? 0 : form;
-    if (a.force == 0 && (env_form == 1 || env_form == 2 || env_form == 6)) a.force = env_form;
+    a.force = form == kShaStream && !stream ? kShaAuto : form;
+    if (a.force == kShaAuto && (env_form == kShaOneWave || env_form == kShaSplit || env_form == kShaLagPair))
+        a.force = env_form;
     if (stream) {
         void* st = nullptr;
         MXEC_TRY(w.scratch(32 * n, &st));
-        a.force = 3;
+        a.force = kShaStream;
         a.work = reinterpret_cast<uint32_t*>(db + o_w);
         a.state = static_cast<uint32_t*>(st);
         // One persistent wave per SIMD: 1.54 TB/s hashed from 65 536 to
@@ -703,7 +704,7 @@ int run_sha_pieces(Device& dev, Slot& slot, hipStream_t s, const std::vector<con
     a.ok = ok_dev;
     a.n = uint32_t(n);
     a.n_cus = uint32_t(dev.n_cus);
-    a.force = 6;
+    a.force = kShaLagPair;
     a.piece.state = state_dev;
     a.piece.slot = reinterpret_cast<const uint32_t*>(db + o_s);
     a.piece.total = reinterpret_cast<const uint64_t*>(db + o_t);

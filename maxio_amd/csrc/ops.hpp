@@ -88,8 +88,7 @@ int run_sha(Device& dev, Slot& slot, hipStream_t s, const std::vector<const uint
             const std::vector<uint64_t>& lens, uint8_t* digests_dev, const uint8_t* expected_dev,
             uint8_t* ok_dev, const std::vector<uint64_t>* exp_idx = nullptr,
             DescArena* arena = nullptr, int form = 0, const uint32_t** tmo_dev = nullptr);
-// One piece of every listed chain (ShaPiece, kernels.hpp), lag quad form
-// with two messages per quad:
+// One piece of every listed chain (ShaPiece, kernels.hpp), lag pair form:
 // message i is the next lens[i] bytes of the chain in state slot slots[i]
 // (state_dev: [slots][8] words, carried between launches on one stream);
 // totals[i] = the message's length if this piece ends it (digest into

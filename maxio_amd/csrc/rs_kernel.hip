@@ -37,12 +37,15 @@
 #include "kernels.hpp"
 
 #include <cstdlib>
-#include <cstring>
 
 namespace mxec {
 namespace {
 
 constexpr int kThreads = 256;
+// 16-byte column vectors per lane per tile of the fast kernels, by the
+// launch's row count: four while the accumulators fit (R <= 4: <= 173 VGPRs,
+// two waves per SIMD), two beyond.
+constexpr int fast_vecs(uint32_t r) { return r <= 4 ? 4 : 2; }
 constexpr uint64_t kEdgeTile = kThreads * 16;  // bytes per edge-kernel step
 
 struct Vec4 {
@@ -159,20 +162,21 @@ typedef uint8_t __attribute__((address_space(1)))* gptr;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// NT: nontemporal (streaming) hint on the loads and stores — every shard
-// byte is touched exactly once per launch.
-template <bool NT>
+// The fast kernels' loads and stores carry the nontemporal (streaming) hint:
+// every shard byte is touched exactly once per launch.  (Plain loads measured
+// 3-6 % slower, plain stores level or slower)  The edge kernel,
+// which runs unaligned launches only, loads plainly.
 __device__ __forceinline__ Vec4 gload16(gcptr p) {
-    const auto* q = (const u32x4 __attribute__((address_space(1)))*)(p);
-    const u32x4 v = NT ? __builtin_nontemporal_load(q) : *q;
+    const u32x4 v = __builtin_nontemporal_load((const u32x4 __attribute__((address_space(1)))*)(p));
     return Vec4{{v.x, v.y, v.z, v.w}};
 }
-template <bool NT>
+__device__ __forceinline__ Vec4 gload16_plain(gcptr p) {
+    const u32x4 v = *(const u32x4 __attribute__((address_space(1)))*)(p);
+    return Vec4{{v.x, v.y, v.z, v.w}};
+}
 __device__ __forceinline__ void gstore16(gptr p, const uint32_t (&w)[4]) {
     u32x4 v = {w[0], w[1], w[2], w[3]};
-    auto* q = (u32x4 __attribute__((address_space(1)))*)(p);
-    if (NT) __builtin_nontemporal_store(v, q);
-    else *q = v;
+    __builtin_nontemporal_store(v, (u32x4 __attribute__((address_space(1)))*)(p));
 }
 
 // Inputs and outputs that a length boundary cuts inside a tile (the short
@@ -358,7 +362,7 @@ __device__ __forceinline__ void edge_step(
         valid = col < len ? int64_t(len - col) : 0;
         p = in_ptrs[uint64_t(obj) * k + j] + col;
         const bool full = aligned && valid >= 16;
-        x = gload16<false>(gcptr(full ? p : safe));
+        x = gload16_plain(gcptr(full ? p : safe));
     };
     // After all four loads are issued: zero what was not a whole vector
     // (selects, no branch), then the rare cut lane reads its bytes.
@@ -478,9 +482,8 @@ __global__ __launch_bounds__(kThreads) void rs_locate_edge(
                               edge_list, steps_per_tile, tile_bytes, aligned, step, nullptr, loc);
 }
 
-template <bool NT>
 __device__ __forceinline__ Vec4 gload16_upto(gcptr p, int32_t valid, gcptr safe) {
-    return mask_tail(gload16<NT>(valid > 0 ? p : safe), valid);
+    return mask_tail(gload16(valid > 0 ? p : safe), valid);
 }
 
 // One tile of one object, 16-byte aligned pointers.  An input whose length
@@ -496,7 +499,7 @@ __device__ __forceinline__ Vec4 gload16_upto(gcptr p, int32_t valid, gcptr safe)
 // first_bad pointer, `row` is the index of its first row there.  kLocate
 // (locate launches): the stored rows loaded and cut the same way, then every
 // row's syndrome at once; loc.rec / loc.off point at the object's entries.
-template <int R, int V, bool NT, bool LNT = NT, int G = 4, int POL = kStore>
+template <int R, int V, int POL = kStore>
 __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, const uint64_t* __restrict__ il,
                                         uint8_t* const* __restrict__ op, const uint64_t* __restrict__ ol,
                                         const uint32_t* __restrict__ tab, uint32_t k, uint32_t stride,
@@ -522,7 +525,7 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
         gcptr p = ((gcptr)(ip[jj])) + lane;
         if (len >= end) {
 #pragma unroll
-            for (int v = 0; v < V; ++v) x[v] = gload16<LNT>(p + v * kThreads * 16);
+            for (int v = 0; v < V; ++v) x[v] = gload16(p + v * kThreads * 16);
         } else if (len <= base) {
 #pragma unroll
             for (int v = 0; v < V; ++v) x[v] = Vec4{{0, 0, 0, 0}};
@@ -530,42 +533,11 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
             const int32_t d = int32_t(len - base) - lane_off;
 #pragma unroll
             for (int v = 0; v < V; ++v)
-                x[v] = gload16_upto<LNT>(p + v * kThreads * 16, d - v * int32_t(kThreads * 16), safe);
+                x[v] = gload16_upto(p + v * kThreads * 16, d - v * int32_t(kThreads * 16), safe);
         }
     };
 
     uint32_t j = 0;
-    if constexpr (G == 8) {
-        // Eight inputs' loads in flight per step (the lab's G = 8 form: with
-        // V = 2 the same bytes in flight per lane as V = 4 x 4 inputs, half
-        // the accumulators, so more waves fit).
-        for (; j + 8 <= k; j += 8) {
-            Vec4 x[8][V];
-            bool full = true;
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) full = full && il[j + jj] >= end;
-            if (full) {
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) {
-                    gcptr p = ((gcptr)(ip[j + jj])) + lane;
-#pragma unroll
-                    for (int v = 0; v < V; ++v) x[jj][v] = gload16<LNT>(p + v * kThreads * 16);
-                }
-            } else {
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) load_in(j + jj, x[jj]);
-            }
-            if constexpr (R >= 3) {
-#pragma unroll
-                for (int jj = 0; jj < 8; jj += 2)
-                    mac_column_pair<R, V>(acc, x[jj], x[jj + 1], tab + (j + jj) * stride * 8,
-                                          tab + (j + jj + 1) * stride * 8);
-            } else {
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) mac_column<R, V>(acc, x[jj], tab + (j + jj) * stride * 8);
-            }
-        }
-    }
     for (; j + 4 <= k; j += 4) {
         Vec4 x[4][V];
         // Wave-uniform: all four inputs reach past this tile (every tile
@@ -578,7 +550,7 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
             for (int jj = 0; jj < 4; ++jj) {
                 gcptr p = ((gcptr)(ip[j + jj])) + lane;
 #pragma unroll
-                for (int v = 0; v < V; ++v) x[jj][v] = gload16<LNT>(p + v * kThreads * 16);
+                for (int v = 0; v < V; ++v) x[jj][v] = gload16(p + v * kThreads * 16);
             }
         } else {
 #pragma unroll
@@ -610,7 +582,7 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
             gcptr o = ((gcptr)(op[i])) + lane;
             if (olen >= end) {
 #pragma unroll
-                for (int v = 0; v < V; ++v) st[i][v] = gload16<LNT>(o + v * kThreads * 16);
+                for (int v = 0; v < V; ++v) st[i][v] = gload16(o + v * kThreads * 16);
             } else if (olen <= base) {
 #pragma unroll
                 for (int v = 0; v < V; ++v)
@@ -622,7 +594,7 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
                 for (int v = 0; v < V; ++v) {
                     const int32_t valid = d - v * int32_t(kThreads * 16);
                     // Masked after the XOR: past the length the two agree.
-                    st[i][v] = gload16<LNT>(valid > 0 ? o + v * kThreads * 16 : safe);
+                    st[i][v] = gload16(valid > 0 ? o + v * kThreads * 16 : safe);
                     if (valid < 16) {
                         Vec4 a{{acc[v][0][i], acc[v][1][i], acc[v][2][i], acc[v][3][i]}};
                         const Vec4 keep = mask_tail(Vec4{{~0u, ~0u, ~0u, ~0u}}, valid);
@@ -689,11 +661,11 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
         for (int v = 0; v < V; ++v) {
             uint32_t ov[4] = {acc[v][0][i], acc[v][1][i], acc[v][2][i], acc[v][3][i]};
             if (olen >= end) {
-                gstore16<NT>(o + v * kThreads * 16, ov);
+                gstore16(o + v * kThreads * 16, ov);
             } else {
                 const int32_t valid = d - v * int32_t(kThreads * 16);
                 if (valid >= 16) {
-                    gstore16<NT>(o + v * kThreads * 16, ov);
+                    gstore16(o + v * kThreads * 16, ov);
                 } else if (valid > 0) {  // the one straddling lane
                     for (int b = 0; b < valid; ++b)
                         o[v * kThreads * 16 + b] = uint8_t(ov[b >> 2] >> (8 * (b & 3)));
@@ -711,7 +683,7 @@ __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, c
 // the object), one wave-uniform scalar load, fetched one tile ahead so it
 // is in SGPRs when the tile starts (the uniform kernel computes the same
 // from the tile index).
-template <int R, int V, bool NT, bool GRP, bool LNT, int G, int POL>
+template <int R, int V, bool GRP, int POL>
 __device__ __forceinline__ void fast_tiles(
     const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
     const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
@@ -745,21 +717,21 @@ __device__ __forceinline__ void fast_tiles(
             lo.rec = loc.rec + obj;
             lo.off = loc.off + obj;
         }
-        rs_tile<R, V, NT, LNT, G, POL>(in_ptrs + in0, in_len + in0, out_ptrs + uint64_t(obj) * r_total + row0,
-                                       out_len + uint64_t(obj) * r_total + row0, coef + coef_off[obj] + row0 * 8, k,
-                                       r_total, base, safe, POL == kCmp ? fb_ptrs + obj : nullptr, row0, lo);
+        rs_tile<R, V, POL>(in_ptrs + in0, in_len + in0, out_ptrs + uint64_t(obj) * r_total + row0,
+                           out_len + uint64_t(obj) * r_total + row0, coef + coef_off[obj] + row0 * 8, k, r_total, base,
+                           safe, POL == kCmp ? fb_ptrs + obj : nullptr, row0, lo);
     }
 }
 
-template <int R, int V, bool NT, bool GRP, int OCC = 1, bool LNT = NT, int G = 4>
-__global__ __launch_bounds__(kThreads, OCC) void rs_apply_fast(
+template <int R, int V, bool GRP>
+__global__ __launch_bounds__(kThreads) void rs_apply_fast(
     const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
     const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
     uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
     const RsTileRec* __restrict__ tiles) {
-    fast_tiles<R, V, NT, GRP, LNT, G, kStore>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform, r_total,
-                                              row0, tiles_per_obj, n_tiles, tiles, nullptr);
+    fast_tiles<R, V, GRP, kStore>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform, r_total, row0,
+                                  tiles_per_obj, n_tiles, tiles, nullptr);
 }
 
 // ReedSolomon::verify: the encode's walk with the compare in place of the
@@ -773,8 +745,8 @@ __global__ __launch_bounds__(kThreads) void rs_verify_fast(
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
     uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
     const RsTileRec* __restrict__ tiles, uint64_t* const* __restrict__ fb_ptrs) {
-    fast_tiles<R, V, true, GRP, true, 4, kCmp>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform,
-                                               r_total, row0, tiles_per_obj, n_tiles, tiles, fb_ptrs);
+    fast_tiles<R, V, GRP, kCmp>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform, r_total, row0,
+                                tiles_per_obj, n_tiles, tiles, fb_ptrs);
 }
 
 // mxec_locate: the verify's geometry and walk with the locate policy
@@ -787,8 +759,8 @@ __global__ __launch_bounds__(kThreads) void rs_locate_fast(
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
     uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
     const RsTileRec* __restrict__ tiles, LocArgs loc) {
-    fast_tiles<R, V, true, GRP, true, 4, kLocate>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform,
-                                                  r_total, row0, tiles_per_obj, n_tiles, tiles, nullptr, loc);
+    fast_tiles<R, V, GRP, kLocate>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform, r_total, row0,
+                                   tiles_per_obj, n_tiles, tiles, nullptr, loc);
 }
 
 // One grouped launch for objects of every output count r <= kMultiR (a
@@ -797,12 +769,12 @@ __global__ __launch_bounds__(kThreads) void rs_locate_fast(
 // out_ptrs / out_len + obj * kMultiR (unused entries length 0), and each
 // tile runs the body compiled for its r (a wave-uniform switch).  One launch
 // instead of one per r: no ramp-down and ramp-up between them.
-template <int V, bool NT>
 __global__ __launch_bounds__(kThreads) void rs_apply_multi(
     const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
     const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint64_t n_tiles,
     const RsTileRec* __restrict__ tiles) {
+    constexpr int V = fast_vecs(kMultiR);
     constexpr uint32_t kTile = kThreads * 16 * V;
     const gcptr safe = (gcptr)(reinterpret_cast<const uint8_t*>(coef));
     RsTileRec next = tiles[blockIdx.x];  // the grid never exceeds n_tiles
@@ -817,10 +789,10 @@ __global__ __launch_bounds__(kThreads) void rs_apply_multi(
         const uint64_t* ol = out_len + uint64_t(cur.obj) * kMultiR;
         const uint32_t* tab = coef + coef_off[cur.obj];
         switch (r) {
-            case 1: rs_tile<1, V, NT>(ip, il, op, ol, tab, k, 1, base, safe); break;
-            case 2: rs_tile<2, V, NT>(ip, il, op, ol, tab, k, 2, base, safe); break;
-            case 3: rs_tile<3, V, NT>(ip, il, op, ol, tab, k, 3, base, safe); break;
-            default: rs_tile<4, V, NT>(ip, il, op, ol, tab, k, 4, base, safe); break;
+            case 1: rs_tile<1, V>(ip, il, op, ol, tab, k, 1, base, safe); break;
+            case 2: rs_tile<2, V>(ip, il, op, ol, tab, k, 2, base, safe); break;
+            case 3: rs_tile<3, V>(ip, il, op, ol, tab, k, 3, base, safe); break;
+            default: rs_tile<4, V>(ip, il, op, ol, tab, k, 4, base, safe); break;
         }
     }
 }
@@ -834,62 +806,54 @@ uint64_t grid_of(const RsArgs& a, int n_cus, int per_cu, uint64_t n) {
     return blocks > n ? n : blocks;
 }
 
-template <int R, int V, bool NT, bool GRP = false, int OCC = 1, bool LNT = NT, int G = 4>
-hipError_t launch_fast(const RsArgs& a, uint32_t tiles_per_obj, uint64_t n_tiles, uint64_t blocks,
-                       hipStream_t s) {
-    hipLaunchKernelGGL((rs_apply_fast<R, V, NT, GRP, OCC, LNT, G>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s,
-                       a.in_ptrs, a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total,
-                       a.row0, tiles_per_obj, n_tiles, a.tiles);
-    return hipGetLastError();
-}
-
 LocArgs loc_args(const RsArgs& a) { return LocArgs{a.locate, a.loc_field, a.loc_tab, a.loc_off}; }
 
-// Verify and locate launches (a.first_bad / a.locate set): the shipping
-// geometry of the same R.
+// An aligned launch of the fast kernels: the encode / decode, or with
+// a.first_bad set the verify of the same geometry.
 template <int R, int V, bool GRP>
-hipError_t launch_verify(const RsArgs& a, uint32_t tiles_per_obj, uint64_t n_tiles, uint64_t blocks,
-                         hipStream_t s) {
-    if (a.locate) {  // the same geometry with the locate policy; one row block of 2..8 rows
-        if constexpr (R >= 2) {
-            if (a.row0 != 0 || a.r != a.r_total) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((rs_locate_fast<R, V, GRP>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
-                               a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
-                               tiles_per_obj, n_tiles, a.tiles, loc_args(a));
-            return hipGetLastError();
-        }
-        return hipErrorInvalidValue;
-    }
-    hipLaunchKernelGGL((rs_verify_fast<R, V, GRP>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
-                       a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
-                       tiles_per_obj, n_tiles, a.tiles, a.first_bad);
+hipError_t launch_fast(const RsArgs& a, uint32_t tiles_per_obj, uint64_t n_tiles, uint64_t blocks,
+                       hipStream_t s) {
+    if (a.first_bad)
+        hipLaunchKernelGGL((rs_verify_fast<R, V, GRP>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
+                           a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
+                           tiles_per_obj, n_tiles, a.tiles, a.first_bad);
+    else
+        hipLaunchKernelGGL((rs_apply_fast<R, V, GRP>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
+                           a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
+                           tiles_per_obj, n_tiles, a.tiles);
     return hipGetLastError();
 }
 
-// Multi-r grouped launches (a.multi): V = 4, nontemporal, rs_group_variant's grid.
+// A locate launch (a.locate set): one row block of 2..8 rows, so its
+// geometry is fast_vecs(R).
+template <int R, bool GRP>
+hipError_t launch_locate(const RsArgs& a, uint32_t tiles_per_obj, uint64_t n_tiles, uint64_t blocks,
+                         hipStream_t s) {
+    if constexpr (R >= 2) {
+        if (a.row0 != 0 || a.r != a.r_total) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((rs_locate_fast<R, fast_vecs(R), GRP>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s,
+                           a.in_ptrs, a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
+                           tiles_per_obj, n_tiles, a.tiles, loc_args(a));
+        return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
+}
+
+// Multi-r grouped launches (a.multi): rs_group_variant's geometry for kMultiR rows.
 hipError_t launch_multi(const RsArgs& a, int n_cus, hipStream_t s) {
     const RsVariant v = rs_group_variant(kMultiR);
     const uint64_t blocks = grid_of(a, n_cus, v.blocks_per_cu, a.n_tiles);
-    hipLaunchKernelGGL((rs_apply_multi<4, true>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
-                       a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.n_tiles, a.tiles);
+    hipLaunchKernelGGL(rs_apply_multi, dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs, a.out_ptrs, a.in_len,
+                       a.out_len, a.coef, a.coef_off, a.n_tiles, a.tiles);
     return hipGetLastError();
 }
 
-// Grouped launches: rs_group_variant's geometry (nontemporal, V = 4 or 2).
+// Grouped launches (r == r_total): rs_group_variant's geometry.
 template <int R>
 hipError_t launch_grouped(const RsArgs& a, int n_cus, hipStream_t s) {
-    const RsVariant v = rs_group_variant(uint32_t(R));
-    const uint64_t blocks = grid_of(a, n_cus, v.blocks_per_cu, a.n_tiles);
-    if (a.first_bad || a.locate) {
-        if constexpr (R <= 4) {
-            if (v.vecs == 4) return launch_verify<R, 4, true>(a, 0, a.n_tiles, blocks, s);
-        }
-        return launch_verify<R, 2, true>(a, 0, a.n_tiles, blocks, s);
-    }
-    if constexpr (R <= 4) {
-        if (v.vecs == 4) return launch_fast<R, 4, true, true>(a, 0, a.n_tiles, blocks, s);
-    }
-    return launch_fast<R, 2, true, true>(a, 0, a.n_tiles, blocks, s);
+    const uint64_t blocks = grid_of(a, n_cus, rs_group_variant(uint32_t(R)).blocks_per_cu, a.n_tiles);
+    if (a.locate) return launch_locate<R, true>(a, 0, a.n_tiles, blocks, s);
+    return launch_fast<R, fast_vecs(R), true>(a, 0, a.n_tiles, blocks, s);
 }
 
 template <int R>
@@ -899,38 +863,14 @@ hipError_t launch_r(const RsArgs& a, int n_cus, hipStream_t s, const RsVariant& 
         const uint32_t tiles_per_obj = uint32_t((a.shard_size + tile - 1) / tile);
         const uint64_t n_tiles = uint64_t(tiles_per_obj) * a.n_obj;
         const uint64_t blocks = grid_of(a, n_cus, var.blocks_per_cu, n_tiles);
-        hipError_t e = hipErrorInvalidValue;
-        if (a.first_bad || a.locate) {  // verify, locate: the shipping geometries only
-            if constexpr (R <= 4) {
-                if (var.vecs == 4) return launch_verify<R, 4, false>(a, tiles_per_obj, n_tiles, blocks, s);
-            }
-            if (var.vecs == 2) return launch_verify<R, 2, false>(a, tiles_per_obj, n_tiles, blocks, s);
-            return e;
-        }
-        if (var.nt && var.load_nt && var.store_nt && var.group == 4 && var.min_waves == 0) {
-            // The shipping geometries (rs_default_variant): V = 4 while the
-            // accumulators fit (R <= 4), V = 2 beyond.
-            if constexpr (R <= 4) {
-                if (var.vecs == 4) return launch_fast<R, 4, true>(a, tiles_per_obj, n_tiles, blocks, s);
-            }
-            if (var.vecs == 2) return launch_fast<R, 2, true>(a, tiles_per_obj, n_tiles, blocks, s);
-        }
-#ifdef MXEC_LAB
-        // Lab geometries (tools/kernel_lab, the MXEC_RS_* lab knobs).
-        if (var.vecs == 1) e = var.nt ? launch_fast<R, 1, true>(a, tiles_per_obj, n_tiles, blocks, s)
-                                      : launch_fast<R, 1, false>(a, tiles_per_obj, n_tiles, blocks, s);
-        else if (R >= 3 && R <= 4 && var.vecs == 2 && var.nt && var.group == 8)  // 8-input steps
-            e = launch_fast<R, 2, true, false, 1, true, 8>(a, tiles_per_obj, n_tiles, blocks, s);
-        else if (var.vecs == 2 && !var.nt) e = launch_fast<R, 2, false>(a, tiles_per_obj, n_tiles, blocks, s);
-        else if (R == 4 && var.vecs == 4 && var.nt && var.min_waves == 3)
-            e = launch_fast<R, 4, true, false, R == 4 ? 3 : 1>(a, tiles_per_obj, n_tiles, blocks, s);
-        else if (R <= 4 && var.vecs == 4 && var.nt && !var.load_nt)  // plain loads, nontemporal stores
-            e = launch_fast<R, 4, true, false, 1, false>(a, tiles_per_obj, n_tiles, blocks, s);
-        else if (R <= 4 && var.vecs == 4 && var.nt && !var.store_nt)  // nontemporal loads, plain stores
-            e = launch_fast<R, 4, false, false, 1, true>(a, tiles_per_obj, n_tiles, blocks, s);
-        else if (R <= 4 && var.vecs == 4 && !var.nt) e = launch_fast<R, 4, false>(a, tiles_per_obj, n_tiles, blocks, s);
-#endif
-        return e;
+        // The launch's geometry is its total row count's (rs_default_variant),
+        // so that every row block shares one tile size: the last block of
+        // more than eight rows in all (R = r_total - 8 <= 4) runs at V = 2.
+        constexpr int V = fast_vecs(R);
+        if (a.locate && var.vecs == V) return launch_locate<R, false>(a, tiles_per_obj, n_tiles, blocks, s);
+        if (!a.locate && var.vecs == V) return launch_fast<R, V, false>(a, tiles_per_obj, n_tiles, blocks, s);
+        if (!a.locate && var.vecs == 2) return launch_fast<R, 2, false>(a, tiles_per_obj, n_tiles, blocks, s);
+        return hipErrorInvalidValue;
     }
     if (a.n_edge && a.edge_tile_bytes != tile) return hipErrorInvalidValue;  // list built for another tile
     if (a.n_edge) {
@@ -968,12 +908,11 @@ hipError_t launch_r(const RsArgs& a, int n_cus, hipStream_t s, const RsVariant& 
 
 uint64_t rs_tile_bytes(const RsVariant& v) { return uint64_t(kThreads) * 16 * uint64_t(v.vecs); }
 
-// Default geometry, from tools/kernel_lab sweeps on MI355X (profiles/): four
-// 16-byte vectors per lane with nontemporal loads/stores while the
-// accumulators fit (R <= 4: <= 173 VGPRs, two waves per SIMD; compiled for
-// three, 164 VGPRs, measured 1.2-1.6 % slower), two beyond that; 512
-// workgroups per CU of grid-stride.  Round 1 swept 4-64 (16 beat 8 and 4,
-// 32 level or +0.9 %); round 2 swept 32-4096 in one process per box: 256
+// Default geometry, from tools/kernel_lab sweeps on MI355X (profiles/):
+// fast_vecs(r_total) vectors per lane (compiled for three waves per SIMD at
+// R = 4, 164 VGPRs, measured 1.2-1.6 % slower) and 512 workgroups per CU of
+// grid-stride.  Round 1 swept 4-64 (16 beat 8 and 4, 32 level or +0.9 %);
+// round 2 swept 32-4096 in one process per box: 256
 // over 32 gains 1.5-4 % in the bench's object-major layout (north star
 // +3.1 %, cfg 4 +2.3 %, cfg 2 +1.5 %, cfg 3 decode +4.1 %) and 3-5 % with
 // data and parity apart, 512 another 0.4-2.1 % / 1-3 %; 1024-2048 gain more
@@ -986,33 +925,16 @@ uint64_t rs_tile_bytes(const RsVariant& v) { return uint64_t(kThreads) * 16 * ui
 // size (and one edge list).
 RsVariant rs_default_variant(uint32_t r_total) {
     RsVariant v;
-    v.vecs = r_total <= 4 ? 4 : 2;
-    v.nt = true;
+    v.vecs = fast_vecs(r_total);
     // R <= 2 (config 2, two-erasure decodes) gained another 0-2 % at 1024 in
     // every layout swept; R = 4 went either way (profiles/r2_lab_rs_grid_*).
     v.blocks_per_cu = r_total <= 2 ? 1024 : 512;
 #ifdef MXEC_LAB
-    // Lab knobs (read per launch; `make lab` builds only):
-    // MXEC_RS_LOAD_NT=0 plain loads with the nontemporal stores (R <= 4);
-    // MXEC_RS_STORE_NT=0 plain stores with the nontemporal loads (R <= 4);
-    // MXEC_RS_G8=1 r = 3, 4 with V = 2 and eight inputs' loads per step;
-    // MXEC_RS_BPC workgroups per CU of uniform launches.
-    if (const char* e = getenv("MXEC_RS_LOAD_NT")) v.load_nt = std::strcmp(e, "0") != 0;
-    if (const char* e = getenv("MXEC_RS_G8"))
-        if (!std::strcmp(e, "1") && r_total >= 3 && r_total <= 4) {
-            v.vecs = 2;
-            v.group = 8;
-        }
-    if (const char* e = getenv("MXEC_RS_STORE_NT")) v.store_nt = std::strcmp(e, "0") != 0;
+    // Lab knob (read per launch; `make lab` builds only): MXEC_RS_BPC,
+    // workgroups per CU of uniform launches.
     if (const char* e = getenv("MXEC_RS_BPC")) {
         const int b = atoi(e);
         if (b > 0 && b <= 4096) v.blocks_per_cu = b;
-    }
-    // MXEC_RS_VECS = 1 | 2 | 4 (4 only for R <= 4): vectors per lane of
-    // uniform launches (the tile is 4 KiB x V per shard).
-    if (const char* e = getenv("MXEC_RS_VECS")) {
-        const int vv = atoi(e);
-        if (vv == 1 || vv == 2 || (vv == 4 && r_total <= 4)) v.vecs = vv;
     }
 #endif
     return v;
@@ -1022,20 +944,15 @@ RsVariant rs_default_variant(uint32_t r_total) {
 // default geometry: config 5 measured 32 / 48 / 64 / 128 / 256 / 2048 /
 // one tile per workgroup within ~1 %, V = 2 3-4 % slower
 // (profiles/r2_rs_group_geometry.txt, r2_rs_grid_bench_ab.txt).
-// MXEC_RS_GROUP_VECS (2 | 4) and MXEC_RS_GROUP_BPC override it in lab builds.
+// MXEC_RS_GROUP_BPC overrides the grid in lab builds.
 RsVariant rs_group_variant(uint32_t r) {
     RsVariant v = rs_default_variant(r);
     v.blocks_per_cu = 512;
 #ifdef MXEC_LAB
-    static const int env_v = [] {
-        const char* e = getenv("MXEC_RS_GROUP_VECS");
-        return e ? atoi(e) : 0;
-    }();
     static const int env_b = [] {
         const char* e = getenv("MXEC_RS_GROUP_BPC");
         return e ? atoi(e) : 0;
     }();
-    if (r <= 4 && (env_v == 2 || env_v == 4)) v.vecs = env_v;
     if (env_b > 0 && env_b <= 4096) v.blocks_per_cu = env_b;
 #endif
     return v;

@@ -7,17 +7,16 @@
 // parallelism is across messages, plus what a round's two halves offer.  The
 // 64 rounds are fully unrolled, rotates are v_alignbit_b32, Σ/σ XOR3, Ch and
 // Maj are one v_bitop3_b32 each (14 VALU per round on one lane).  Forms, by
-// batch size: the lag quad form (up to 48 messages per CU: a producer wave
-// computes K + W, each message's e-side and a-side rounds run on two lanes of
-// a consumer wave, the a-side two rounds behind, 9 VALU per step; the default
-// latency form, with a piece mode that carries chains across launches), the
-// same-round quad form (lab A/B), the split (producer / consumer) form with
-// one lane per message, one wave per 64 messages, and the persistent stream
-// form for batches of more groups than the chip has SIMDs (below).  Per
-// message the work is a VALU-latency chain (see DESIGN.md for the roofline),
-// not HBM-bound.
+// batch size (ShaForm, kernels.hpp): the lag pair form (up to 64 messages per
+// CU: two producer waves compute K + W, each message's e-side and a-side
+// rounds run on two lanes of a consumer wave, the a-side two rounds behind,
+// 9 VALU per step; the latency form, with a piece mode that carries chains
+// across launches), the split (producer / consumer) form with one lane per
+// message, one wave per 64 messages, and the persistent stream form for
+// batches of more groups than the chip has SIMDs (below).  Per message the
+// work is a VALU-latency chain (see DESIGN.md for the roofline), not
+// HBM-bound.
 #include <cstdlib>
-#include <cstring>
 
 #include "hash_device.hpp"
 #include "kernels.hpp"
@@ -103,8 +102,8 @@ __global__ __launch_bounds__(64) void sha256_kernel(const uint8_t* const* __rest
 // (W[16..63]) depends only on the message bytes, not on the state, so a
 // second wave of the same workgroup computes K[t] + W[t] for block b+1 into
 // LDS while the first wave runs the 64 rounds of block b: the serial wave's
-// stream drops from ~1500 to ~950 instructions per block.  LDS is
-// double-buffered, laid out [buf][t/4][lane] x 16 B so each ds_read_b128 /
+// stream drops from ~1500 to ~950 instructions per block.  LDS is a ring of
+// three buffers, laid out [buf][t/4][lane] x 16 B so each ds_read_b128 /
 // ds_write_b128 is 64 consecutive 16-byte slots (conflict-free).
 // ---------------------------------------------------------------------------
 
@@ -149,16 +148,6 @@ __device__ __forceinline__ void load_kw(const u32x4* kwl, u32x4 (&v)[16]) {
     for (int q = 0; q < 16; ++q) v[q] = kwl[q * ROW];
 }
 
-#ifdef MXEC_LAB
-// 64 rounds reading K + W from LDS: all 16 reads issued up front so their
-// latency overlaps the first rounds (the split form's two-buffer ring, lab).
-__device__ __forceinline__ void compress_kw(uint32_t (&st)[8], const u32x4* kwl) {
-    u32x4 v[16];
-    load_kw(kwl, v);
-    compress_regs(st, v);
-}
-#endif
-
 __constant__ uint32_t kK256[64] = {
     0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
     0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
@@ -169,8 +158,8 @@ __constant__ uint32_t kK256[64] = {
     0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
     0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
 
-// Producer: K + W of one block (w = its 16 big-endian words) into LDS.
-template <int ROW = 64>
+// Producer with one lane per message (the split form's): K + W of one block
+// (w = its 16 big-endian words) into LDS, rows 64 columns apart.
 __device__ __forceinline__ void schedule_kw(uint32_t (&w)[16], u32x4* dst) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -178,12 +167,10 @@ __device__ __forceinline__ void schedule_kw(uint32_t (&w)[16], u32x4* dst) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int t = 4 * q + u;
-#ifndef MXEC_LAB_SHA_NOSCHED
             if (t >= 16) SHA_W(t);
-#endif
             o[u] = w[t & 15] + kK256[t];
         }
-        dst[q * ROW] = u32x4{o[0], o[1], o[2], o[3]};
+        dst[q * 64] = u32x4{o[0], o[1], o[2], o[3]};
     }
 }
 
@@ -203,19 +190,11 @@ __device__ __forceinline__ void schedule_kw(uint32_t (&w)[16], u32x4* dst) {
 // the step before: a v_cndmask picks which), and both store what arrives in
 // B[s - 1].  Each lane writes K + W of its own words into the message's LDS
 // column (rows of four words: components L and L + 2).  kown[k] = K[2k + L].
-// The K + W ring's barriers (producer and consumer sides).  Diagnostic
-// build `make nosync` (MXEC_LAB_SHA_NOSYNC): none at all -- every wave runs
-// its loop unsynchronised (wrong digests, same work), so the form's block
-// time without the barriers and the waits behind them.
-#ifdef MXEC_LAB_SHA_NOSYNC
-#define KW_SYNC() ((void)0)
-#else
-#define KW_SYNC() __syncthreads()
-#endif
-
 #define QDPP_SWAP(x) uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0xB1, 0xF, 0xF, true))  // quad_perm [1,0,3,2]
 
-template <int ROW>
+constexpr int kQuadRow = 66;  // u32x4 per K + W row of the lag pair form: 64 messages, zeros, ones
+constexpr int kShaRing = 3;   // K + W buffers of the split and lag pair forms' LDS ring
+
 __device__ __forceinline__ void schedule_kw_pair(const uint32_t (&w)[16], bool odd, const uint32_t (&kown)[32],
                                                  uint32_t* col) {
     uint32_t A[8], B[8];
@@ -226,8 +205,8 @@ __device__ __forceinline__ void schedule_kw_pair(const uint32_t (&w)[16], bool o
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        col[q * ROW * 4] = A[2 * q] + kown[2 * q];
-        col[q * ROW * 4 + 2] = A[2 * q + 1] + kown[2 * q + 1];
+        col[q * kQuadRow * 4] = A[2 * q] + kown[2 * q];
+        col[q * kQuadRow * 4 + 2] = A[2 * q + 1] + kown[2 * q + 1];
     }
 #pragma unroll
     for (int s = 8; s < 32; ++s) {
@@ -237,8 +216,8 @@ __device__ __forceinline__ void schedule_kw_pair(const uint32_t (&w)[16], bool o
         if (s < 31) B[(s - 1) & 7] = QDPP_SWAP(odd ? prev : x);
         if (s & 1) {  // row (s - 1) / 2 has both of this lane's words
             const int q = s >> 1;
-            col[q * ROW * 4] = prev + kown[s - 1];
-            col[q * ROW * 4 + 2] = x + kown[s];
+            col[q * kQuadRow * 4] = prev + kown[s - 1];
+            col[q * kQuadRow * 4 + 2] = x + kown[s];
         }
     }
 }
@@ -264,25 +243,26 @@ __device__ __forceinline__ void message_words(const uint8_t* p, bool aligned, ui
 constexpr int kShaPrefetch = 4;
 __device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 
-// The producer wave of the split and quad forms: K + W of blocks 0 .. nmax-1
-// of the wave's 64 messages (one per lane; `live` lanes with `nfull` full
-// blocks each) into the NB-buffer LDS ring kw[NB][16][ROW] at column `lane`.
-// Blocks 0 .. NB-2 are written before a first barrier, block b + NB - 1
-// before the barrier that opens block b: 1 + nmax barriers in all, which the
-// consumer waves match.
-// PAIR2: two lanes per message (schedule_kw_pair; lane & 1 = the parity,
-// `col` = the message's LDS column); otherwise one lane per message in column
-// `lane` (schedule_kw).
+// A producer wave of the split and lag pair forms: K + W of blocks
+// 0 .. nmax-1 of the wave's messages (`live` lanes with `nfull` full blocks
+// each) into the LDS ring kw[kShaRing][16][row].  Blocks 0 and 1 are written
+// before a first barrier, block b + 2 before the barrier that opens block b:
+// 1 + nmax barriers in all, which the consumer waves match.
+// PAIR2 (the lag pair form): two lanes per message (schedule_kw_pair;
+// lane & 1 = the parity, `col` = the message's LDS column), rows of kQuadRow;
+// otherwise (the split form) one lane per message in column `lane`
+// (schedule_kw), rows of 64.
 // With PAIR2 a producer wave holds half of the workgroup's messages, so the
 // workgroup-wide facts come from the caller: `wg_donor`, a message of nmax
 // blocks (the re-read target of lanes without blocks), and `wg_aligned`,
 // whether every message of the workgroup is 16-byte aligned.
-template <int NB, int ROW, bool PAIR2 = false>
+template <bool PAIR2>
 __device__ __forceinline__ void kw_producer(u32x4* kw, uint32_t lane, bool live, const uint8_t* p,
                                             uint64_t nfull, uint64_t nmax, bool aligned, uint32_t col = 0,
                                             const uint8_t* wg_donor = nullptr, bool wg_aligned = true) {
+    constexpr int NB = kShaRing;
     constexpr int AHEAD = NB - 1;  // blocks the producer runs ahead of the consumer
-    constexpr int BUF = 16 * ROW;  // u32x4 per buffer
+    constexpr int BUF = 16 * (PAIR2 ? kQuadRow : 64);  // u32x4 per buffer
     uint32_t w[16];
     const bool odd = (lane & 1) != 0;
     uint32_t kown[32];  // K[2k + parity] (PAIR2)
@@ -292,9 +272,9 @@ __device__ __forceinline__ void kw_producer(u32x4* kw, uint32_t lane, bool live,
     }
     auto schedule = [&](uint32_t buf) {
         if constexpr (PAIR2)
-            schedule_kw_pair<ROW>(w, odd, kown, reinterpret_cast<uint32_t*>(kw + buf * BUF + col) + (odd ? 1 : 0));
+            schedule_kw_pair(w, odd, kown, reinterpret_cast<uint32_t*>(kw + buf * BUF + col) + (odd ? 1 : 0));
         else
-            schedule_kw<ROW>(w, kw + buf * BUF + lane);
+            schedule_kw(w, kw + buf * BUF + lane);
     };
     if (PAIR2 ? wg_aligned : __all(!live || nfull == 0 || aligned)) {
         // Every message 16-byte aligned: the raw bytes of the next
@@ -332,7 +312,7 @@ __device__ __forceinline__ void kw_producer(u32x4* kw, uint32_t lane, bool live,
                 schedule(uint32_t(j));
             }
         }
-        KW_SYNC();
+        __syncthreads();
         // Whole groups of kShaPrefetch steps, then the rest: an exit in the
         // middle of a group would join the loop's back edge with fewer loads
         // issued, and the waits at the top would drain the ring again.
@@ -348,7 +328,7 @@ __device__ __forceinline__ void kw_producer(u32x4* kw, uint32_t lane, bool live,
                 load_block(ps + 64 * min_u64(b + AHEAD + kShaPrefetch, last), ring[j]);
                 schedule(wb);
                 wb = wb + 1 == NB ? 0 : wb + 1;
-                KW_SYNC();
+                __syncthreads();
             }
         }
 #pragma unroll
@@ -357,7 +337,7 @@ __device__ __forceinline__ void kw_producer(u32x4* kw, uint32_t lane, bool live,
                 block_words(ring[j], w);
                 schedule(wb);
                 wb = wb + 1 == NB ? 0 : wb + 1;
-                KW_SYNC();
+                __syncthreads();
             }
         }
     } else {
@@ -368,7 +348,7 @@ __device__ __forceinline__ void kw_producer(u32x4* kw, uint32_t lane, bool live,
                 message_words(p + 64 * j, aligned, w);
                 schedule(uint32_t(j));
             }
-        KW_SYNC();
+        __syncthreads();
         uint32_t wb = AHEAD % NB;
         for (uint64_t b = 0; b < nmax; ++b) {
             if (b + AHEAD < nfull) {
@@ -376,27 +356,25 @@ __device__ __forceinline__ void kw_producer(u32x4* kw, uint32_t lane, bool live,
                 schedule(wb);
             }
             wb = wb + 1 == NB ? 0 : wb + 1;
-            KW_SYNC();
+            __syncthreads();
         }
     }
 }
 
-// NB = 3 (default): the producer runs two blocks ahead, so the consumer
-// issues block b+1's 16 LDS reads right after the barrier that opens block b
-// and runs block b's rounds from registers: no read latency at the top of a
-// block and one wait per block instead of one per four rounds.  NB = 2 is
-// the earlier one-ahead form (MXEC_SHA_SPLIT_BUFS=2, lab).  Buffer of block
-// b: b % NB; 16 KiB each.
-template <int NB>
+// The producer runs two blocks ahead, so the consumer issues block b+1's 16
+// LDS reads right after the barrier that opens block b and runs block b's
+// rounds from registers: no read latency at the top of a block and one wait
+// per block instead of one per four rounds (the earlier one-ahead, two-buffer
+// ring read each block's K + W at the top of its rounds).  Buffer of block
+// b: b % kShaRing; 16 KiB each.
 __global__ __launch_bounds__(128) void sha256_split_kernel(const uint8_t* const* __restrict__ ptrs,
                                                            const uint64_t* __restrict__ lens,
                                                            uint8_t* __restrict__ digests,
                                                            const uint8_t* __restrict__ expected,
                                                            const uint64_t* __restrict__ exp_idx,
                                                            uint8_t* __restrict__ ok, uint32_t n, uint32_t prio) {
-    static_assert(NB == 2 || NB == 3, "two or three K+W buffers");
     sha_priority(prio);
-    __shared__ u32x4 kw[NB][16][64];
+    __shared__ u32x4 kw[kShaRing][16][64];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t i = blockIdx.x * 64 + lane;
     const bool live = i < n;
@@ -422,40 +400,31 @@ __global__ __launch_bounds__(128) void sha256_split_kernel(const uint8_t* const*
     // The two roles run separate loops with one barrier per block each plus
     // one before the first (the trip counts match, so the barriers pair up).
     if (wave == 0) {
-        KW_SYNC();
-        if constexpr (NB == 2) {
-#ifdef MXEC_LAB
-            for (uint64_t b = 0; b < nmax; ++b) {
-                if (b < nfull) compress_kw(st, &kw[b & 1][0][lane]);
-                KW_SYNC();
-            }
-#endif
-        } else {
-            // Blocks 0 and 1 were written before the first barrier; block
-            // b+1 before the barrier that opens block b.  Two register sets
-            // swap roles every block (the loop is unrolled by two), and the
-            // reads of a block past the last land in registers nobody uses.
-            u32x4 cur[16], nxt[16];
-            load_kw(&kw[0][0][lane], cur);
-            // Retire these reads here: otherwise the loop's first wait, sized
-            // for 32 reads in flight on entry, also stalls every later block
-            // on its just-issued prefetch (lgkmcnt counts to 15).
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-            uint32_t rb = 1;  // buffer of the block after the current one
-            for (uint64_t b = 0; b < nmax; b += 2) {
-                load_kw(&kw[rb][0][lane], nxt);
-                if (b < nfull) compress_regs(st, cur);
-                KW_SYNC();
-                rb = rb == 2 ? 0 : rb + 1;
-                if (b + 1 >= nmax) break;
-                load_kw(&kw[rb][0][lane], cur);
-                if (b + 1 < nfull) compress_regs(st, nxt);
-                KW_SYNC();
-                rb = rb == 2 ? 0 : rb + 1;
-            }
+        __syncthreads();
+        // Blocks 0 and 1 were written before the first barrier; block
+        // b+1 before the barrier that opens block b.  Two register sets
+        // swap roles every block (the loop is unrolled by two), and the
+        // reads of a block past the last land in registers nobody uses.
+        u32x4 cur[16], nxt[16];
+        load_kw(&kw[0][0][lane], cur);
+        // Retire these reads here: otherwise the loop's first wait, sized
+        // for 32 reads in flight on entry, also stalls every later block
+        // on its just-issued prefetch (lgkmcnt counts to 15).
+        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+        uint32_t rb = 1;  // buffer of the block after the current one
+        for (uint64_t b = 0; b < nmax; b += 2) {
+            load_kw(&kw[rb][0][lane], nxt);
+            if (b < nfull) compress_regs(st, cur);
+            __syncthreads();
+            rb = rb == 2 ? 0 : rb + 1;
+            if (b + 1 >= nmax) break;
+            load_kw(&kw[rb][0][lane], cur);
+            if (b + 1 < nfull) compress_regs(st, nxt);
+            __syncthreads();
+            rb = rb == 2 ? 0 : rb + 1;
         }
     } else {
-        kw_producer<NB, 64>(&kw[0][0][0], lane, live, p, nfull, nmax, aligned);
+        kw_producer<false>(&kw[0][0][0], lane, live, p, nfull, nmax, aligned);
     }
     if (wave == 1 || !live) return;
     const uint32_t rem = uint32_t(len - nfull * 64);
@@ -482,82 +451,23 @@ __global__ __launch_bounds__(128) void sha256_split_kernel(const uint8_t* const*
 }
 
 // ---------------------------------------------------------------------------
-// Quad form for latency-bound batches (at most 48 messages per CU).
+// Lag pair form for latency-bound batches (at most kShaLagMsgs per CU).
 //
 // The split form's consumer sits on the one-lane floor: 14 VALU per round
 // (Σ1, Ch, Σ0, Maj, the adds), issued one every ~4.4 cycles by one wave.
-// Here four lanes of a consumer wave serve one message, and the e-side and
-// a-side halves of a round run as the SAME instructions in two lanes with
-// per-lane operands:
-//   lane E (4j):       X = e, rotations 6/11/25 -> Σ1(e); Ch(e, f, g)
-//   lane A (4j + 1):   X = a, rotations 2/13/22 -> Σ0(a); Maj(a, b, c)
-//   lanes 4j + 2, + 3: all zero (the zero source of the DPP reads below).
+// Here two lanes of a consumer wave serve one message, and the e-side and
+// a-side halves of a round run as the SAME instructions in the two lanes
+// with per-lane operands:
+//   lane E (2j):       X = e, rotations 6/11/25 -> Σ1(e); Ch(e, f, g)
+//   lane A (2j + 1):   X = a, rotations 2/13/22 -> Σ0(a); Maj(a, b, c)
 // Maj(a, b, c) = Ch(~(a ^ b), b, c), so one v_bitop3 makes the selector
-// (e in lane E, ~(a ^ b) in lane A) and one more is Ch in both lanes.  With
-// H = h + d + K + W in lane E and -d in lane A,
-//   P  = Σ + Ch + H       is d + T1 = e' in lane E and T2 - d in lane A;
-//   X' = P + P[lane E]    (one v_add_u32 with a quad_perm DPP source)
-// is e' in lane E (its DPP source is a zero lane) and T1 + T2 = a' in lane A.
-// The next round's H is X[t-2] + X[t-2][lane A] (h + d in lane E, d in lane
-// A: DPP again), then one v_xad_u32: xor with a per-lane mask (all ones in
-// lane A: ~d + 1 = -d) plus the K + W word (K + W in lane E, 1 in lane A, 0
-// in the zero lanes).  10 VALU per round instead of 14; the idle lanes cost
-// nothing, the chain being bound by the wave's issue rate.
+// (e in lane E, ~(a ^ b) in lane A) and one more is Ch in both lanes.
 //
-// A workgroup is one producer wave (the split form's, kw_producer: K + W of
-// 48 messages, one per lane) and three consumer waves of 16 messages each,
-// so each wave has a SIMD of its own.  K + W rows are kQuadRow columns wide:
-// 0..47 the producer's, 64 all zero and 65 all one, so every consumer lane
-// reads its word at the same row offset from its own column.  The padded
-// tail (1 or 2 blocks) runs in lane E after the main loop, one-lane form.
-// ---------------------------------------------------------------------------
-constexpr int kQuadRow = 66;  // u32x4 per K + W row: 64 producer lanes, zeros, ones
-
-#define QDPP(x, ctrl) uint32_t(__builtin_amdgcn_update_dpp(0, int(x), (ctrl), 0xF, 0xF, true))
-#ifdef MXEC_LAB
-constexpr int kQuadFromE = 0xA2;   // quad_perm [2, 0, 2, 2]: lane A reads lane E, the rest a zero lane
-constexpr int kQuadFromA = 0xA9;   // quad_perm [1, 2, 2, 2]: lane E reads lane A, the rest a zero lane
-#endif
-constexpr int kQuadBcastA = 0x55;  // quad_perm [1, 1, 1, 1]
-constexpr int kPairBcastA = 0xF5;  // quad_perm [1, 1, 3, 3]: each message's lane A to its lane E
-
-struct QuadLane {
-    uint32_t sh1, sh2, sh3;  // rotations: Σ1's in lane E, Σ0's in lane A
-    uint32_t ma;             // all ones in lane A (selector ~(a ^ b); negated d), else 0
-};
-
-#ifdef MXEC_LAB
-// One block.  s[0..3] = (e, f, g, h) in lane E, (a, b, c, d) in lane A, zero
-// in the zero lanes; v = the block's K + W rows as this lane reads them.
-__device__ __forceinline__ void compress_quad(uint32_t (&s)[4], const u32x4 (&v)[16], const QuadLane& q) {
-    uint32_t x[4];  // x[t & 3] = X[t]; X[-1], X[-2], X[-3] = s[1], s[2], s[3]
-    x[0] = s[0];
-    x[3] = s[1];
-    x[2] = s[2];
-    x[1] = s[3];
-    uint32_t h = ((x[1] + QDPP(x[1], kQuadFromA)) ^ q.ma) + v[0].x;
-#pragma unroll
-    for (int t = 0; t < 64; ++t) {
-        const uint32_t X0 = x[t & 3], X1 = x[(t + 3) & 3], X2 = x[(t + 2) & 3];
-        const uint32_t S = xor3(rotr(X0, q.sh1), rotr(X0, q.sh2), rotr(X0, q.sh3));
-        const uint32_t sel = __builtin_amdgcn_bitop3_b32(X0, X1, q.ma, 0xD2);  // X0 ^ (~X1 & ma)
-        const uint32_t P = S + bsel(sel, X1, X2) + h;
-        if (t < 63) h = ((X2 + QDPP(X2, kQuadFromA)) ^ q.ma) + v[(t + 1) >> 2][(t + 1) & 3];
-        x[(t + 1) & 3] = P + QDPP(P, kQuadFromE);
-    }
-    s[0] += x[0];
-    s[1] += x[3];
-    s[2] += x[2];
-    s[3] += x[1];
-}
-#endif
-
-// Lag variant (the auto quad form; MXEC_SHA_FORM=lag pins it).  Above, lane A's
-// a' = T1 + T2 needs lane E's T1 of the same round, so a DPP add sits on
-// every round's critical path (X -> rotations -> xor3 -> add3 -> DPP add ->
-// X'): the rounds measured ~54 cycles for 10 VALU.  Here lane A runs
-// TWO rounds behind lane E (tools/sha_lag_model.py is the lane-level model,
-// checked against hashlib):
+// Lane A's a' = T1 + T2 needs lane E's T1.  Taking it in the same round (the
+// first quad form, since removed) put a DPP add on every round's critical
+// path (X -> rotations -> xor3 -> add3 -> DPP add -> X'): its rounds measured
+// ~54 cycles for 10 VALU.  Here lane A runs TWO rounds behind lane E
+// (tools/sha_lag_model.py is the lane-level model, checked against hashlib):
 //   step t, lane E:  e[t+1] = Σ1(e[t]) + Ch(e[t], e[t-1], e[t-2]) + H,
 //                    H = e[t-3] + a[t-3] + K[t] + W[t]         (h + d + K + W)
 //   step t, lane A:  a[t-1] = Σ0(a[t-2]) + Maj(a[t-2], a[t-3], a[t-4]) + H,
@@ -570,9 +480,26 @@ __device__ __forceinline__ void compress_quad(uint32_t (&s)[4], const u32x4 (&v)
 // A block is 66 steps (lane A's last two rounds run beside two unused lane-E
 // values); lane A's first two outputs are forced to the known b and a, and
 // lane A keeps its state rotated as (c, d, a, b) so both lanes load the ring
-// from, and mostly add back, the same slots.  Lanes 2 and 3 of a quad swap
-// among themselves and compute nothing anyone reads.
-constexpr int kLagSwap = 0xB1;  // quad_perm [1, 0, 3, 2]
+// from, and mostly add back, the same slots.  No lane idles, so a DPP quad
+// holds two messages (lanes 0-1 and 2-3, each pair swapping within itself).
+//
+// A workgroup is two producer waves of 32 messages, two lanes per message
+// (schedule_kw_pair), waves 0-1, and two consumer waves of 32, waves 2-3: 64
+// messages on four waves, one per SIMD.  (One producer wave of 64 lanes ran
+// neck and neck with the consumers and the barriers cost the difference;
+// DESIGN §4.)  K + W rows are kQuadRow columns wide: 0..63 the messages', 64
+// all zero and 65 all one, so lane E reads K + W and lane A its constant at
+// the same row offset from its own column.  The padded tail (1 or 2 blocks)
+// runs in lane E after the main loop, one-lane form.
+// ---------------------------------------------------------------------------
+#define QDPP(x, ctrl) uint32_t(__builtin_amdgcn_update_dpp(0, int(x), (ctrl), 0xF, 0xF, true))
+constexpr int kLagSwap = 0xB1;     // quad_perm [1, 0, 3, 2]
+constexpr int kPairBcastA = 0xF5;  // quad_perm [1, 1, 3, 3]: each message's lane A to its lane E
+
+struct QuadLane {
+    uint32_t sh1, sh2, sh3;  // rotations: Σ1's in lane E, Σ0's in lane A
+    uint32_t ma;             // all ones in lane A (selector ~(a ^ b); negated d), else 0
+};
 
 // (X3 ^ ma) + c as one v_xad: left free, the compiler sums X3 ^ ma, c and a
 // v_mov_dpp with an add3 (10 VALU per step instead of 9).
@@ -589,15 +516,7 @@ __device__ __forceinline__ uint32_t lag_xc(uint32_t x3, uint32_t ma, uint32_t c)
 // floor; a hand order spacing every on-chain pair two slots apart, held
 // with sched_barriers, measured 1.48 us per block against 1.265
 // (profiles/r3/sha_lag/ab_order.jsonl).
-//
-// `at(t)` runs at the top of step t (the caller's K + W reads for the next
-// block, spread over the block: sha256_quad_kernel LDG).
-struct NoStep {
-    __device__ __forceinline__ void operator()(int) const {}
-};
-template <class AT = NoStep>
-__device__ __forceinline__ void compress_lag(uint32_t (&s)[4], const u32x4 (&v)[16], const QuadLane& q,
-                                             const AT& at = AT()) {
+__device__ __forceinline__ void compress_lag(uint32_t (&s)[4], const u32x4 (&v)[16], const QuadLane& q) {
     const bool is_a = q.ma != 0;
     const uint32_t one = q.ma & 1;  // c after lane E's rounds: 1 in lane A (-X3 = ~X3 + 1), 0 elsewhere
     uint32_t x[8];
@@ -612,7 +531,6 @@ __device__ __forceinline__ void compress_lag(uint32_t (&s)[4], const u32x4 (&v)[
     uint32_t xc = lag_xc(x[6], q.ma, v[0][1]);
 #pragma unroll
     for (int t = 0; t < 66; ++t) {
-        at(t);
         const uint32_t X0 = x[t & 7], X1 = x[(t + 7) & 7], X2 = x[(t + 6) & 7];
         const uint32_t S = xor3(rotr(X0, q.sh1), rotr(X0, q.sh2), rotr(X0, q.sh3));
         const uint32_t sel = __builtin_amdgcn_bitop3_b32(X0, X1, q.ma, 0xD2);  // X0 ^ (~X1 & ma)
@@ -634,22 +552,13 @@ __device__ __forceinline__ void compress_lag(uint32_t (&s)[4], const u32x4 (&v)[
     s[3] += is_a ? x[1] : x[5];
 }
 
-// LAG: compress_lag (default) or the same-round compress_quad (lab A/B).
-// PAIR (lag only; MXEC_SHA_FORM=lagpair, lab): two messages per quad -- the
-// lag form needs no zero lanes, so lanes 4j+2 / 4j+3 run a second message's
-// E and A sides -- and a workgroup is the producer wave (64 messages) plus two
-// consumer waves of 32: 64 messages per workgroup of three waves.
-// P2 (PAIR only; the auto form): two producer waves of 32 messages, two
-// lanes per message (schedule_kw_pair), waves 0-1; consumers waves 2-3: a
-// workgroup of four waves, one per SIMD.
-// LDG (lag forms): the next block's 16 ds_read_b128 of K + W go out in LDG
-// groups spread over the current block -- group g at the top of step
-// 64 g / LDG -- instead of all 16 right after the barrier.  A wave may hold
-// at most 15 LDS instructions in flight (lgkmcnt is 4 bits), so the 16th
-// read of a burst waited for the first to come back, and the in-order wave
-// issued no VALU meanwhile (round 5: ~260 cycles per block above the step
-// lab's 66 x 37.4).
-template <bool LAG, bool PAIR = false, bool P2 = false, int LDG = 1>
+// The next block's 16 ds_read_b128 of K + W all go out right after the
+// barrier that opens the current one.  A wave holds at most 15 LDS
+// instructions in flight (lgkmcnt is 4 bits), so the 16th read of the burst
+// waits for the first; spreading the reads over the block's steps instead (2
+// or 4 groups, or 15 + 1) measured 10-14 % slower, one read among the chain's
+// VALU costing far more than the burst's wait, so the burst
+// stays.
 __global__ __launch_bounds__(256) void sha256_quad_kernel(const uint8_t* const* __restrict__ ptrs,
                                                          const uint64_t* __restrict__ lens,
                                                          uint8_t* __restrict__ digests,
@@ -657,11 +566,9 @@ __global__ __launch_bounds__(256) void sha256_quad_kernel(const uint8_t* const* 
                                                          const uint64_t* __restrict__ exp_idx,
                                                          uint8_t* __restrict__ ok, uint32_t n, uint32_t prio,
                                                          ShaPiece pc) {
-    static_assert(LAG || !PAIR, "two messages per quad needs the lag form (no zero lanes)");
-    static_assert(PAIR || !P2, "two producer waves serve the two-messages-per-quad consumers");
-    constexpr uint32_t PW = P2 ? 2 : 1;  // producer waves
-    constexpr int NB = 3, BUF = 16 * kQuadRow;
-    constexpr uint32_t MSGS = PAIR ? 64 : kShaQuadMsgs;  // messages per workgroup
+    constexpr uint32_t PW = 2;  // producer waves
+    constexpr int NB = kShaRing, BUF = 16 * kQuadRow;
+    constexpr uint32_t MSGS = kShaLagMsgs;  // messages per workgroup
     sha_priority(prio);
     __shared__ u32x4 kw[NB][16][kQuadRow];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -671,7 +578,7 @@ __global__ __launch_bounds__(256) void sha256_quad_kernel(const uint8_t* const* 
     }
     const uint32_t base = blockIdx.x * MSGS;
     // Every wave derives the same trip count from the workgroup's messages
-    // (one per lane below kShaQuadMsgs), so the barriers pair up.
+    // (one per lane), so the barriers pair up.
     const uint32_t pi = base + lane;
     const bool plive = lane < MSGS && pi < n;
     const uint8_t* pp = plive ? ptrs[pi] : nullptr;
@@ -684,29 +591,23 @@ __global__ __launch_bounds__(256) void sha256_quad_kernel(const uint8_t* const* 
     }
     nmax = (uint64_t(__builtin_amdgcn_readfirstlane(uint32_t(nmax >> 32))) << 32) |
            __builtin_amdgcn_readfirstlane(uint32_t(nmax));
-    if constexpr (P2) {
-        if (wave < PW) {  // producer wave `wave`: messages 32 * wave + lane / 2, two lanes each
-            // The workgroup-wide donor and alignment, from the one-lane-per-
-            // message view (pi = base + lane) every wave holds.
-            const uint64_t dmask = __ballot(plive && pfull == nmax);
-            const int dl = dmask ? __ffsll((unsigned long long)dmask) - 1 : 0;
-            const uint8_t* wdonor = reinterpret_cast<const uint8_t*>(__shfl(reinterpret_cast<uintptr_t>(pp), dl));
-            const bool waligned = __all(!plive || pfull == 0 || (reinterpret_cast<uintptr_t>(pp) & 15) == 0);
-            const uint32_t mi = wave * 32 + (lane >> 1), qi = base + mi;
-            const bool qlive = qi < n;
-            const uint8_t* qp = qlive ? ptrs[qi] : nullptr;
-            const uint64_t qfull = qlive ? lens[qi] / 64 : 0;
-            kw_producer<NB, kQuadRow, true>(&kw[0][0][0], lane, qlive, qp, qfull, nmax,
-                                            (reinterpret_cast<uintptr_t>(qp) & 15) == 0, mi, wdonor, waligned);
-            return;
-        }
-    } else if (wave == 0) {
-        kw_producer<NB, kQuadRow>(&kw[0][0][0], lane, plive, pp, pfull, nmax,
-                                  (reinterpret_cast<uintptr_t>(pp) & 15) == 0);
+    if (wave < PW) {  // producer wave `wave`: messages 32 * wave + lane / 2, two lanes each
+        // The workgroup-wide donor and alignment, from the one-lane-per-
+        // message view (pi = base + lane) every wave holds.
+        const uint64_t dmask = __ballot(plive && pfull == nmax);
+        const int dl = dmask ? __ffsll((unsigned long long)dmask) - 1 : 0;
+        const uint8_t* wdonor = reinterpret_cast<const uint8_t*>(__shfl(reinterpret_cast<uintptr_t>(pp), dl));
+        const bool waligned = __all(!plive || pfull == 0 || (reinterpret_cast<uintptr_t>(pp) & 15) == 0);
+        const uint32_t mi = wave * 32 + (lane >> 1), qi = base + mi;
+        const bool qlive = qi < n;
+        const uint8_t* qp = qlive ? ptrs[qi] : nullptr;
+        const uint64_t qfull = qlive ? lens[qi] / 64 : 0;
+        kw_producer<true>(&kw[0][0][0], lane, qlive, qp, qfull, nmax, (reinterpret_cast<uintptr_t>(qp) & 15) == 0, mi,
+                          wdonor, waligned);
         return;
     }
-    const uint32_t role = PAIR ? lane & 1 : lane & 3;
-    const uint32_t ml = PAIR ? (wave - PW) * 32 + (lane >> 1) : (wave - 1) * 16 + (lane >> 2);
+    const uint32_t role = lane & 1;  // 0: lane E, 1: lane A
+    const uint32_t ml = (wave - PW) * 32 + (lane >> 1);
     const uint32_t i = base + ml;
     const bool live = i < n;
     const uint8_t* p = live ? ptrs[i] : nullptr;
@@ -721,82 +622,43 @@ __global__ __launch_bounds__(256) void sha256_quad_kernel(const uint8_t* const* 
     // ok and running state are indexed by the slot).
     const uint32_t slot = live && pc.state ? pc.slot[i] : i;
     uint32_t s[4] = {0, 0, 0, 0};
-    if (live && pc.state && pc.resume && role < 2) {  // continue the chain (a..h in state[slot])
+    if (live && pc.state && pc.resume) {  // continue the chain (a..h in state[slot])
         const uint32_t* sv = pc.state + 8 * uint64_t(slot);
         if (role == 0) {
             s[0] = sv[4]; s[1] = sv[5]; s[2] = sv[6]; s[3] = sv[7];
-        } else if (LAG) {  // (c, d, a, b)
+        } else {  // (c, d, a, b)
             s[0] = sv[2]; s[1] = sv[3]; s[2] = sv[0]; s[3] = sv[1];
-        } else {
-            s[0] = sv[0]; s[1] = sv[1]; s[2] = sv[2]; s[3] = sv[3];
         }
     } else if (role == 0) {
         s[0] = 0x510e527fu; s[1] = 0x9b05688cu; s[2] = 0x1f83d9abu; s[3] = 0x5be0cd19u;
-    } else if (role == 1 && LAG) {  // (c, d, a, b)
+    } else {  // (c, d, a, b)
         s[0] = 0x3c6ef372u; s[1] = 0xa54ff53au; s[2] = 0x6a09e667u; s[3] = 0xbb67ae85u;
-    } else if (role == 1) {
-        s[0] = 0x6a09e667u; s[1] = 0xbb67ae85u; s[2] = 0x3c6ef372u; s[3] = 0xa54ff53au;
     }
-    const u32x4* kcol = &kw[0][0][role == 0 ? ml : role == 1 ? 65 : 64];
-    // As the split form's NB = 3 consumer: block b + 1's reads go out right
-    // after the barrier that opens block b, block b runs from registers.
-    KW_SYNC();
+    const u32x4* kcol = &kw[0][0][role == 0 ? ml : 65];
+    // As the split form's consumer: block b + 1's reads go out right after
+    // the barrier that opens block b, block b runs from registers.
+    __syncthreads();
     u32x4 cur[16], nxt[16];
     load_kw<kQuadRow>(kcol, cur);
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-    static_assert(LDG == 1 || LDG == 2 || LDG == 4 || LDG == 15, "K + W read groups: 1, 2, 4 or 15 + 1");
-    // LDG 15: rows 0-14 after the barrier, row 15 at the top of step 2 (a
-    // burst of 15 fits lgkmcnt; the 16th no longer waits for the first).
-    constexpr int NG = LDG == 15 ? 2 : LDG;  // read groups
-    constexpr int RPG = 16 / NG;             // rows per read group (LDG 1, 2, 4)
-    // Group g's rows of the block in ring buffer `buf` into `dst`.
-    auto rows = [&](u32x4 (&dst)[16], uint32_t buf, int g) {
-        const int r0 = LDG == 15 ? (g ? 15 : 0) : g * RPG, r1 = LDG == 15 ? (g ? 16 : 15) : (g + 1) * RPG;
-#pragma unroll
-        for (int r = r0; r < r1; ++r) dst[r] = kcol[buf * BUF + r * kQuadRow];
-    };
-    auto at_step = [&](u32x4 (&dst)[16], uint32_t buf, int t) {
-        if constexpr (LDG == 15) {
-            if (t == 2) rows(dst, buf, 1);
-        } else if (LDG > 1 && t > 0 && t < 64 && t % (64 / LDG) == 0) {
-            rows(dst, buf, t / (64 / LDG));
-        }
-    };
     uint32_t rb = 1;
     for (uint64_t b = 0; b < nmax; b += 2) {
-        rows(nxt, rb, 0);
-        if (b < nfull) {
-#ifdef MXEC_LAB
-            if constexpr (!LAG) {
-                for (int g = 1; g < NG; ++g) rows(nxt, rb, g);
-                compress_quad(s, cur, q);
-            } else
-#endif
-            compress_lag(s, cur, q, [&](int t) { at_step(nxt, rb, t); });
-        }  // a lane past its message's blocks never reads K + W again: no reads here
-        KW_SYNC();
+        load_kw<kQuadRow>(kcol + rb * BUF, nxt);
+        if (b < nfull) compress_lag(s, cur, q);  // a lane past its message's blocks only keeps the barriers
+        __syncthreads();
         rb = rb == 2 ? 0 : rb + 1;
         if (b + 1 >= nmax) break;
-        rows(cur, rb, 0);
-        if (b + 1 < nfull) {
-#ifdef MXEC_LAB
-            if constexpr (!LAG) {
-                for (int g = 1; g < NG; ++g) rows(cur, rb, g);
-                compress_quad(s, nxt, q);
-            } else
-#endif
-            compress_lag(s, nxt, q, [&](int t) { at_step(cur, rb, t); });
-        }  // a lane past its message's blocks never reads K + W again: no reads here
-        KW_SYNC();
+        load_kw<kQuadRow>(kcol + rb * BUF, cur);
+        if (b + 1 < nfull) compress_lag(s, nxt, q);
+        __syncthreads();
         rb = rb == 2 ? 0 : rb + 1;
     }
-    // Lane E takes (a, b, c, d) from lane A and finishes alone: padded tail,
-    // digest, expected-digest check.  (The lag form's lane A holds
-    // (c, d, a, b).)
+    // Lane E takes (a, b, c, d) from lane A, which holds (c, d, a, b), and
+    // finishes alone: padded tail, digest, expected-digest check.
     uint32_t st[8];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        st[t] = QDPP(s[LAG ? (t + 2) & 3 : t], PAIR ? kPairBcastA : kQuadBcastA);
+        st[t] = QDPP(s[(t + 2) & 3], kPairBcastA);
         st[4 + t] = s[t];
     }
     if (role != 0 || !live) return;
@@ -1035,38 +897,13 @@ __global__ __launch_bounds__(256) void sha256_stream_kernel(const uint8_t* const
 // profiles/r2_sha_stream_lab_sizes.jsonl).
 constexpr uint32_t kSplitMaxMessages = 256 * 4 * 64 * 3 / 4;
 
-// The quad form the auto choice takes (up to kShaLagMsgs per CU): 4 =
-// same-round, 5 = lag, 6 = lag with two messages per quad.  6 against 5 on
-// config 3's 10 240 x 1 MiB: 20.72 vs 20.89 ms; at 16 000 messages (past 5's
-// 48 per CU) 20.93 ms against the split form's 27.5 (profiles/r3/sha_lag/).
-// Forms 4 and 5 and the split form's two-buffer ring exist in lab builds
-// only (`make lab`, -DMXEC_LAB).
-constexpr int kShaQuadAuto = 6;
-// K + W read groups of the auto form's consumers (sha256_quad_kernel LDG;
-// lab builds A/B it with MXEC_SHA_LDG=1|2|4|15).  Spreading the next block's
-// reads over the block lost: 10 240 x 1 MiB took
-// 22.0 ms with two groups and 22.4 with four against 19.6 with all 16 reads
-// after the barrier, on one box in interleaved fresh processes
-// (profiles/r6/sha_ldg_ab.jsonl), and 15 after the barrier with the 16th at
-// step 2 (same 605 VALU) took 21.7 against 19.7 (sha_ldg15_ab_r6ag.jsonl):
-// one read among the chain's VALU costs far more than the burst's wait.
-constexpr int kShaLdg = 1;
-
 #ifdef MXEC_LAB
-// MXEC_SHA_SPLIT_BUFS=2: the split form's one-ahead K+W ring (lab A/B; read
-// per launch), default 3.
-int split_bufs() {
-    const char* e = getenv("MXEC_SHA_SPLIT_BUFS");
-    return e && atoi(e) == 2 ? 2 : 3;
-}
-
 // MXEC_SHA_PRIO=0..3 (lab A/B; read per launch), default 3.
 uint32_t sha_prio() {
     const char* e = getenv("MXEC_SHA_PRIO");
     return e ? uint32_t(atoi(e)) : 3u;
 }
 #else
-constexpr int split_bufs() { return 3; }
 constexpr uint32_t sha_prio() { return 3u; }
 #endif
 
@@ -1074,75 +911,39 @@ hipError_t launch_sha256(const ShaArgs& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
     const uint32_t blocks = (a.n + 63) / 64;
     int form = a.force;
-    if (form == 0) {
-        // Auto: the lag pair form while its workgroups fit one per CU, then
-        // split, then one wave per 64 messages.  (The host pins a form
-        // through a.force: MXEC_SHA_FORM, read into the context's knobs.)
+    if (form == kShaAuto) {
+        // The lag pair form while its workgroups fit one per CU (at 16 000
+        // messages still 20.93 ms against the split form's 27.5,
+        // profiles/r3/sha_lag/), then split, then one wave per 64 messages.
+        // (The host pins a form through a.force: MXEC_SHA_FORM, read into
+        // the context's knobs.)
         const uint64_t n_cus = a.n_cus ? a.n_cus : 256;
-#ifdef MXEC_LAB
-        // Lab builds: MXEC_SHA_FORM=quad|lag selects the lab quad forms.
-        const char* env = getenv("MXEC_SHA_FORM");
-        if (env && !strcmp(env, "quad")) form = 4;
-        else if (env && !strcmp(env, "lag")) form = 5;
-        else
-#endif
-        form = a.n <= kShaLagMsgs * n_cus ? kShaQuadAuto : a.n <= kSplitMaxMessages ? 2 : 1;
+        form = a.n <= kShaLagMsgs * n_cus ? kShaLagPair : a.n <= kSplitMaxMessages ? kShaSplit : kShaOneWave;
     }
-    if (a.piece.state && form != 4 && form != 5 && form != 6) return hipErrorInvalidValue;  // piece mode: quad forms
-#ifdef MXEC_LAB
-    if (form == 4 || form == 5) {  // 4: the same-round quad, 5: the lag quad (lab A/B)
-        const dim3 grid((a.n + kShaQuadMsgs - 1) / kShaQuadMsgs);
-        hipLaunchKernelGGL(form == 5 ? sha256_quad_kernel<true> : sha256_quad_kernel<false>, grid, dim3(256), 0, s,
-                           a.ptrs, a.lens, a.digests, a.expected, a.exp_idx, a.ok, a.n, sha_prio(), a.piece);
-        return hipGetLastError();
-    }
-#else
-    if (form == 4 || form == 5) return hipErrorInvalidValue;
-#endif
-    if (form == 6) {  // the lag quad, two messages per quad, two producer waves (the auto form)
-#ifdef MXEC_LAB
-        if (const char* e = getenv("MXEC_SHA_PRODUCERS"); e && atoi(e) == 1) {  // lab A/B: one producer wave
-            hipLaunchKernelGGL((sha256_quad_kernel<true, true, false>), dim3((a.n + 63) / 64), dim3(192), 0, s, a.ptrs,
+    if (a.piece.state && form != kShaLagPair) return hipErrorInvalidValue;  // piece mode: lag pair only
+    switch (form) {
+        case kShaLagPair:
+            hipLaunchKernelGGL(sha256_quad_kernel, dim3((a.n + kShaLagMsgs - 1) / kShaLagMsgs), dim3(256), 0, s, a.ptrs,
                                a.lens, a.digests, a.expected, a.exp_idx, a.ok, a.n, sha_prio(), a.piece);
-            return hipGetLastError();
+            break;
+        case kShaStream: {
+            const uint32_t per = a.wg_waves ? a.wg_waves : 1;
+            if (!a.work || !a.state || a.waves == 0 || a.seg_max == 0 || per > 4 || a.waves % per)
+                return hipErrorInvalidValue;
+            hipLaunchKernelGGL(sha256_stream_kernel, dim3(a.waves / per), dim3(64 * per), 0, s, a.ptrs, a.lens,
+                               a.digests, a.expected, a.exp_idx, a.ok, a.n, a.work, a.state, a.seg_max, sha_prio());
+            break;
         }
-#endif
-#ifdef MXEC_LAB
-        if (const char* e = getenv("MXEC_SHA_LDG"); e && atoi(e) != kShaLdg) {  // lab A/B: K + W read groups
-            const int g = atoi(e);
-            auto* kern = g == 1    ? &sha256_quad_kernel<true, true, true, 1>
-                         : g == 2  ? &sha256_quad_kernel<true, true, true, 2>
-                         : g == 15 ? &sha256_quad_kernel<true, true, true, 15>
-                                   : &sha256_quad_kernel<true, true, true, 4>;
-            hipLaunchKernelGGL(kern, dim3((a.n + 63) / 64), dim3(256), 0, s, a.ptrs, a.lens, a.digests, a.expected,
-                               a.exp_idx, a.ok, a.n, sha_prio(), a.piece);
-            return hipGetLastError();
-        }
-#endif
-        hipLaunchKernelGGL((sha256_quad_kernel<true, true, true, kShaLdg>), dim3((a.n + 63) / 64), dim3(256), 0, s,
-                           a.ptrs, a.lens, a.digests, a.expected, a.exp_idx, a.ok, a.n, sha_prio(), a.piece);
-        return hipGetLastError();
+        case kShaSplit:
+            hipLaunchKernelGGL(sha256_split_kernel, dim3(blocks), dim3(128), 0, s, a.ptrs, a.lens, a.digests,
+                               a.expected, a.exp_idx, a.ok, a.n, sha_prio());
+            break;
+        case kShaOneWave:
+            hipLaunchKernelGGL(sha256_kernel, dim3(blocks), dim3(64), 0, s, a.ptrs, a.lens, a.digests, a.expected,
+                               a.exp_idx, a.ok, a.n, sha_prio());
+            break;
+        default: return hipErrorInvalidValue;
     }
-    if (form == 3) {
-        const uint32_t per = a.wg_waves ? a.wg_waves : 1;
-        if (!a.work || !a.state || a.waves == 0 || a.seg_max == 0 || per > 4 || a.waves % per) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(sha256_stream_kernel, dim3(a.waves / per), dim3(64 * per), 0, s, a.ptrs, a.lens, a.digests,
-                           a.expected, a.exp_idx, a.ok, a.n, a.work, a.state, a.seg_max, sha_prio());
-        return hipGetLastError();
-    }
-    const bool split = form == 2;
-#ifdef MXEC_LAB
-    if (split && split_bufs() == 2)
-        hipLaunchKernelGGL(sha256_split_kernel<2>, dim3(blocks), dim3(128), 0, s, a.ptrs, a.lens,
-                           a.digests, a.expected, a.exp_idx, a.ok, a.n, sha_prio());
-    else
-#endif
-    if (split)
-        hipLaunchKernelGGL(sha256_split_kernel<3>, dim3(blocks), dim3(128), 0, s, a.ptrs, a.lens,
-                           a.digests, a.expected, a.exp_idx, a.ok, a.n, sha_prio());
-    else
-        hipLaunchKernelGGL(sha256_kernel, dim3(blocks), dim3(64), 0, s, a.ptrs, a.lens, a.digests,
-                           a.expected, a.exp_idx, a.ok, a.n, sha_prio());
     return hipGetLastError();
 }
 

@@ -375,21 +375,14 @@ def test_short_last_chunk_device_encode_and_rebuild(ctx, last):
 
 
 # MXEC_SHA_FORM pins the SHA-256 kernel (read at mxec_open, so each form has
-# its own context).  Shipping forms: lagpair (the auto form up to 64
-# messages per CU: the lag quad, four lanes per message behind a producer
-# wave, the a-side two rounds behind the e-side, two messages per quad),
-# split (producer/consumer waves) and one (one wave per 64 messages).  Lab
-# builds (make lab, MXEC_LIB) add lag (one message per quad) and quad (the
-# same-round quad form).
-SHA_FORMS = ["lagpair", "split", "one", "lag", "quad"]
-LAB_SHA_FORMS = {"lag", "quad"}
+# its own context): lagpair (the auto form up to 64 messages per CU: two
+# lanes per message behind two producer waves, the a-side two rounds behind
+# the e-side), split (producer/consumer waves) and one (one wave per 64
+# messages).
+SHA_FORMS = ["lagpair", "split", "one"]
 
 
 def _form_ctx(ctx_with, form):
-    from conftest import lab_build
-
-    if form in LAB_SHA_FORMS and not lab_build():
-        pytest.skip(f"SHA form {form!r} exists in lab builds only")
     return ctx_with(MXEC_SHA_FORM=form)
 
 

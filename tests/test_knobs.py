@@ -3,9 +3,8 @@
 * The MXEC_* names inside libmaxio_ec.so (the strings its getenv calls use)
   are exactly the ones INTEGRATION.md §3's product and test-only tables
   document, and the lab build's extra names are the lab list.
-* The shipping library instantiates only the default kernel geometries
-  (no lab RS variants, no lab SHA forms): the verdict-r3 lab surface stays
-  in `make lab` builds.
+* The shipping library instantiates exactly the kernel geometries a launch
+  can reach, and a lab build the same ones.
 """
 from __future__ import annotations
 
@@ -52,26 +51,39 @@ def test_lab_build_adds_only_the_documented_lab_knobs():
 
 
 def _kernels(path):
+    """The library's rs_*_fast and sha256_ kernels, as 'name<args>' without
+    namespaces (the fat binary's symbols: one local data symbol per kernel)."""
     out = subprocess.run(["nm", "-C", path], capture_output=True, text=True, check=True).stdout
-    return {re.sub(r"\(.*", "", ln.split(" ", 2)[2].replace("(anonymous namespace)", "anon"))
-            for ln in out.splitlines()
-            if " d " in ln and ("rs_apply" in ln or "sha256_" in ln) and ".kd" not in ln}
+    names = [re.sub(r"\(.*", "", ln.split(" ", 2)[2].replace("(anonymous namespace)", "anon"))
+             for ln in out.splitlines()
+             if " d " in ln and ("_fast<" in ln or "sha256_" in ln) and ".kd" not in ln]
+    return sorted(n.replace("void ", "").split("::")[-1] for n in names)
+
+
+def _fast_set(family, uniform_v2, r_min=1):
+    """R = r_min..8, uniform and grouped, at V = 4 for R <= 4 and 2 beyond;
+    uniform_v2: also the uniform R <= 4 kernels at V = 2, which the last row
+    block of a launch of 9..12 rows in all runs (the launch's tile size is
+    its total row count's)."""
+    want = [f"{family}<{r}, {4 if r <= 4 else 2}, {grp}>" for r in range(r_min, 9) for grp in ("false", "true")]
+    if uniform_v2:
+        want += [f"{family}<{r}, 2, false>" for r in range(r_min, 5)]
+    return sorted(want)
 
 
 def test_product_library_has_only_default_kernel_instantiations():
+    """Exactly the kernels a launch can reach; a lab build, where present,
+    holds the same ones (its knobs change launch parameters only)."""
     if not os.path.exists(LIB):
         pytest.skip("libmaxio_ec.so not built")
     ks = _kernels(LIB)
-    fast = {k for k in ks if "rs_apply_fast<" in k}
-    for k in fast:
-        r, v, nt, grp, occ, lnt, g = re.search(r"rs_apply_fast<(.*)>", k).group(1).split(", ")
-        # V = 4 only for R <= 4; always nontemporal, one wave target, 4 inputs per step
-        assert (nt, occ, lnt, g) == ("true", "1", "true", "4"), k
-        assert v == "2" or (v == "4" and int(r) <= 4), k
-    assert len(fast) == 4 * 2 + 8 * 2  # R 1..4 x V 4 + R 1..8 x V 2, uniform and grouped
-    sha = {k for k in ks if "sha256_" in k}
-    assert not any("sha256_quad_kernel<true, false>" in k or "sha256_quad_kernel<false" in k for k in sha), sha
-    assert not any("sha256_split_kernel<2>" in k for k in sha), sha
+    if os.path.exists(LAB):
+        assert _kernels(LAB) == ks
+    assert [k for k in ks if k.startswith("rs_apply_fast<")] == _fast_set("rs_apply_fast", True)
+    assert [k for k in ks if k.startswith("rs_verify_fast<")] == _fast_set("rs_verify_fast", True)
+    assert [k for k in ks if k.startswith("rs_locate_fast<")] == _fast_set("rs_locate_fast", False, r_min=2)
+    assert [k for k in ks if k.startswith("sha256_")] == [
+        "sha256_kernel", "sha256_quad_kernel", "sha256_split_kernel", "sha256_stream_kernel"]
 
 
 def test_entry_point_count_matches_the_docs():

@@ -2,8 +2,8 @@
 //
 // Calibrates the HBM ceiling with plain streaming kernels (copy, read-only,
 // write-only, and the RS access pattern with the GF math removed: read k
-// shards, write m shards) and sweeps the interior RS kernel's knobs
-// (RsVariant) on the BASELINE shapes.  Development tool, not product; prints
+// shards, write m shards) and sweeps the interior RS kernel's grid
+// (RsVariant's blocks_per_cu, at the shipping geometry) on the BASELINE shapes.  Development tool, not product; prints
 // one JSON object per measurement.
 //
 //   make -C tools && tools/kernel_lab [n_obj_cfg2]
@@ -275,8 +275,8 @@ int main(int argc, char** argv) {
     const bool sha_only = argc > 2 && !std::strcmp(argv[2], "sha");
     const bool sha_big = argc > 2 && !std::strcmp(argv[2], "shabig");
     const bool hbm_only = argc > 2 && !std::strcmp(argv[2], "hbm");
-    // `kernel_lab N ns`: every geometry of the north-star shape (k=8 m=4, 1 MiB)
-    // against the 2:1 no-math pattern, two rounds.
+    // `kernel_lab N ns`: the default grids on the north-star shape (k=8 m=4,
+    // 1 MiB) and its neighbours, alternating, three rounds.
     const bool ns_only = argc > 2 && !std::strcmp(argv[2], "ns");
     // ---- calibration ----
     if (hbm_only) {
@@ -348,7 +348,7 @@ int main(int argc, char** argv) {
         report("pattern_4r2w", "k4m2 S10MiB", ms, double(n2) * 6 * S2);
     }
 
-    // ---- RS variants ----
+    // ---- RS grids ----
     auto sweep = [&](Shape sh, const char* name, bool full) {
         auto mat = mxec::rs_matrix(sh.k, sh.r);
         mxec::GfMatrix rows(sh.r, sh.k);
@@ -357,34 +357,23 @@ int main(int argc, char** argv) {
         uint32_t* coef = nullptr;
         Batch b(buf, buf + sh.n * sh.k * sh.S, sh, mxec::coef_tables(rows), &coef);
         const double bytes = double(sh.n) * (sh.k + sh.r) * sh.S;
+        // The shipping geometry at each grid.  (An LDS-DMA ring form, a
+        // contiguous-run tile order, V = 1, plain loads / stores and the
+        // three-waves build were measured here and dropped: profiles/r1_lab_*,
+        // profiles/r2_lab_ns_occupancy.jsonl, DESIGN_HISTORY.md.)
+        std::vector<int> grids;
+        if (hbm_only) grids = {8, 16, 32};
+        else if (ns_only) grids = {512, 1024, 512, 1024, 512, 1024};
+        else if (full) grids = {8, 64, 512, 1024};
+        else grids = {mxec::rs_default_variant(uint32_t(sh.r)).blocks_per_cu};
         std::vector<mxec::RsVariant> vs;
-        if (hbm_only) {
-            // (An LDS-DMA ring form of this kernel and a contiguous-run tile
-            // order were measured here and dropped: profiles/r1_lab_rs_glds_variants.jsonl,
-            // profiles/r1_lab_hbm_ceilings_tile_order.jsonl.)
-            for (int bpc : {8, 16, 32}) vs.push_back(mxec::RsVariant{4, true, bpc});
-        } else if (ns_only) {
-            // V = 4: workgroups per CU of grid-stride, alternating, three
-            // rounds; MXEC_LAB_MW=3 adds the R = 4 kernel compiled for 3
-            // waves per SIMD (164 VGPRs against 173: measured 1.2-1.6 %
-            // slower, profiles/r2_lab_ns_occupancy.jsonl)
-            const bool mw = getenv("MXEC_LAB_MW") != nullptr;
-            for (int rep = 0; rep < 3; ++rep)
-                for (int bpc : {512, 1024}) {
-                    vs.push_back(mxec::RsVariant{4, true, bpc, 0});
-                    vs.push_back(mxec::RsVariant{2, true, bpc, 0});
-                    if (mw) vs.push_back(mxec::RsVariant{4, true, bpc, 3});
-                }
-        } else if (full) {
-            for (int v : {1, 2, 4})
-                for (bool nt : {false, true})
-                    for (int bpc : {4, 8, 16}) vs.push_back(mxec::RsVariant{v, nt, bpc});
-        } else {
-            for (int v : {1, 2, 4})
-                for (bool nt : {false, true}) vs.push_back(mxec::RsVariant{v, nt, 8});
+        for (int bpc : grids) {
+            mxec::RsVariant v = mxec::rs_default_variant(uint32_t(sh.r));
+            v.blocks_per_cu = bpc;
+            vs.push_back(v);
         }
-        // Reference output of the default register kernel, for a bit-exact
-        // check of every variant (hbm mode).
+        // Reference output at the first grid, for a bit-exact check of every
+        // other (hbm and ns modes).
         uint8_t* par = buf + sh.n * sh.k * sh.S;
         const uint64_t par_bytes = sh.n * sh.r * sh.S;
         uint8_t* ref = nullptr;
@@ -393,7 +382,7 @@ int main(int argc, char** argv) {
         if (check) {
             CK(hipMalloc(&ref, par_bytes));
             CK(hipMalloc(&bad, 8));
-            CK(mxec::launch_rs_apply_variant(b.a, cus, 0, mxec::RsVariant{4, true, 16}));
+            CK(mxec::launch_rs_apply_variant(b.a, cus, 0, vs[0]));
             CK(hipMemcpy(ref, par, par_bytes, hipMemcpyDeviceToDevice));
         }
         for (const auto& v : vs) {
@@ -405,12 +394,12 @@ int main(int argc, char** argv) {
                                    reinterpret_cast<const u32x4*>(ref), par_bytes / 16, bad);
                 unsigned long long nb = 0;
                 CK(hipMemcpy(&nb, bad, 8, hipMemcpyDeviceToHost));
-                std::printf("{\"what\": \"check\", \"v\": %d, \"bpc\": %d, \"min_waves\": %d, \"bad16\": %llu}\n",
-                            v.vecs, v.blocks_per_cu, v.min_waves, nb);
+                std::printf("{\"what\": \"check\", \"v\": %d, \"bpc\": %d, \"bad16\": %llu}\n", v.vecs,
+                            v.blocks_per_cu, nb);
             }
             double ms = tm.median_ms([&] { CK(mxec::launch_rs_apply_variant(b.a, cus, 0, v)); });
             char nm[96];
-            std::snprintf(nm, sizeof nm, "rs_v%d_nt%d_bpc%d_mw%d", v.vecs, int(v.nt), v.blocks_per_cu, v.min_waves);
+            std::snprintf(nm, sizeof nm, "rs_v%d_bpc%d", v.vecs, v.blocks_per_cu);
             report(nm, name, ms, bytes);
         }
         (void)hipFree(coef);
@@ -418,7 +407,7 @@ int main(int argc, char** argv) {
         if (bad) (void)hipFree(bad);
     };
     // ---- SHA-256: one lane per message ----
-    auto sha = [&](uint64_t n, uint64_t L, const char* name, int force = 0) {
+    auto sha = [&](uint64_t n, uint64_t L, const char* name, int force = mxec::kShaAuto) {
         std::vector<const uint8_t*> ptrs(n);
         std::vector<uint64_t> lens(n, L);
         for (uint64_t i = 0; i < n; ++i) ptrs[i] = buf + i * L;
@@ -443,9 +432,9 @@ int main(int argc, char** argv) {
         for (uint64_t n : {16384ull, 49152ull, 65536ull, 81920ull}) {
             char nm[96];
             std::snprintf(nm, sizeof nm, "%llu x 1 MiB split form", (unsigned long long)n);
-            sha(n, 1ull << 20, nm, 2);
+            sha(n, 1ull << 20, nm, mxec::kShaSplit);
             std::snprintf(nm, sizeof nm, "%llu x 1 MiB one-wave form", (unsigned long long)n);
-            sha(n, 1ull << 20, nm, 1);
+            sha(n, 1ull << 20, nm, mxec::kShaOneWave);
         }
         CK(hipFree(buf));
         return 0;
@@ -461,16 +450,16 @@ int main(int argc, char** argv) {
     if (hbm_only) {
         sweep(Shape{4, 2, S2, n2}, "k4m2 S10MiB (cfg2)", true);
         sweep(Shape{8, 4, 1ull << 20, n2 * 60 / 12}, "k8m4 S1MiB (north star)", true);
-        sha(10240, 1ull << 20, "10240 x 1 MiB split form", 2);
+        sha(10240, 1ull << 20, "10240 x 1 MiB split form", mxec::kShaSplit);
         // (32 and 16 messages per wave of the split form measured 2.70 / 2.76
         // us per block against 1.82: profiles/r1_lab_sha_lanes_per_wave.jsonl.)
         CK(hipFree(buf));
         return 0;
     }
     sha(10240, 1ull << 20, "10240 x 1 MiB (cfg3 verify)");
-    sha(10240, 1ull << 20, "10240 x 1 MiB split form", 2);
-    sha(10240, 1ull << 20, "10240 x 1 MiB one-wave form", 1);
-    sha(1024, 10ull << 20, "1024 x 10 MiB split form", 2);
+    sha(10240, 1ull << 20, "10240 x 1 MiB split form", mxec::kShaSplit);
+    sha(10240, 1ull << 20, "10240 x 1 MiB one-wave form", mxec::kShaOneWave);
+    sha(1024, 10ull << 20, "1024 x 10 MiB split form", mxec::kShaSplit);
     if (sha_only) {
         CK(hipFree(buf));
         return 0;

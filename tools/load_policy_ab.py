@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Within-process A/B of RS kernel knobs on the bench's own buffers,
-alternating rounds, HIP-event timed; then the guide's float4 copy on the
-same buffers.  Config 2 and the north-star shape.  Lab tool, not product.
+"""Within-process A/B of a lab knob read per launch on the bench's own
+buffers, alternating rounds, HIP-event timed; then the guide's float4 copy on
+the same buffers.  Config 2 and the north-star shape.  Lab tool, not product.
+(Its first use, nontemporal against plain loads, is closed: plain loads
+measured 3-6 % slower and that kernel form is gone, DESIGN_HISTORY.md.)
 
   python tools/load_policy_ab.py [--rounds 4] [--reps 10]
-      nontemporal loads (default) vs plain loads, both with nontemporal
-      stores (MXEC_RS_LOAD_NT, read per launch)
-  python tools/load_policy_ab.py --env MXEC_RS_BPC --values 512,1024,2048
+      workgroups per CU of uniform RS launches (MXEC_RS_BPC): the default
+      grid against 1024 and 2048
+  python tools/load_policy_ab.py --env MXEC_SHA_PRIO --values 3,0 --configs 3
       any knob read per launch, one arm per value ("" = unset)
 """
 from __future__ import annotations
@@ -29,8 +31,8 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--configs", default="2,ns")
-    ap.add_argument("--env", default="MXEC_RS_LOAD_NT")
-    ap.add_argument("--values", default="1,0")
+    ap.add_argument("--env", default="MXEC_RS_BPC")
+    ap.add_argument("--values", default=",1024,2048")
     a = ap.parse_args()
     import torch
 

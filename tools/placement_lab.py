@@ -51,7 +51,7 @@ def main() -> int:
     ap.add_argument("--spacer-mib", default="", help="comma list: MiB allocated ahead of each batch (cycled)")
     ap.add_argument("--variants", default="",
                     help="semicolon list of name=ENV:val,ENV:val (lab RS knobs, e.g. "
-                         "'v2=MXEC_RS_VECS:2;st=MXEC_RS_STORE_NT:0'), each timed like a grid")
+                         "'g=MXEC_RS_GROUP_BPC:256;c=MXEC_CRC_BPC:8'), each timed like a grid")
     ap.add_argument("--shape", default="4,2,10", help="k,m,chunk MiB (default configs[1]: 4,2,10)")
     ap.add_argument("--base-pad-kib", type=int, default=-1,
                     help="the batch's own shard pad (default: 2112 KiB at chunks >= 4 MiB, else 0, as bench.py)")

@@ -2,7 +2,7 @@
 """SHA-256 of n device-resident messages alone (mxec_sha256_batch_device),
 HIP-event timed on its stream: the configs[2] hash launch without the
 verify / rebuild around it, for A/B of library builds (MXEC_LIB), including
-diagnostic builds whose digests are wrong (make nosched / nosync).
+diagnostic builds whose digests are wrong.
 
   python tools/sha_alone.py [--n 10240] [--mib 1] [--reps 5]
 """
