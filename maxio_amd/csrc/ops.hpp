@@ -136,9 +136,10 @@ int decode_plan(Device& dev, int k, int m, const uint8_t* present, bool data_onl
 constexpr uint64_t kSlotAlign = 256;
 inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
-// Runs an entry point body; no C++ exception crosses the C ABI.
+// Runs an entry point body; no C++ exception crosses the C ABI.  Returns
+// what the body returns (int, or int64_t for a byte count or an error).
 template <class F>
-int guarded(F&& f) {
+auto guarded(F&& f) -> decltype(f()) {
     try {
         return f();
     } catch (const std::bad_alloc&) {

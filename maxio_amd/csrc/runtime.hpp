@@ -17,12 +17,10 @@
 #include <vector>
 
 #include "../../include/maxio_ec.h"
+#include "error.hpp"
 #include "knobs.hpp"
 
 namespace mxec {
-
-int set_error(int code, const std::string& msg);
-const char* last_error();
 
 #define MXEC_HIP(expr)                                                                  \
     do {                                                                                \
@@ -30,12 +28,6 @@ const char* last_error();
         if (_e != hipSuccess)                                                           \
             return ::mxec::set_error(_e == hipErrorOutOfMemory ? MXEC_E_OOM : MXEC_E_DEVICE, \
                                      std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-#define MXEC_TRY(expr)              \
-    do {                            \
-        int _rc = (expr);           \
-        if (_rc != MXEC_OK) return _rc; \
     } while (0)
 
 // ensure(n): at least n bytes (a re-size frees the old buffer, and hipFree

@@ -1,5 +1,5 @@
 // scrub_plan.hpp — what a scrub's findings amount to (mxec_scrub_object,
-// storage.cpp): shard states -> damaged count -> whether a heal may run ->
+// storage_scrub.cpp): shard states -> damaged count -> whether a heal may run ->
 // verdict.
 //
 // Host-only (no HIP, no I/O): built into libmaxio_ec.so and, on its own with

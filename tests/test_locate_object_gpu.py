@@ -1,6 +1,6 @@
 """GPU: mxec_locate_object -- the scrub's cheap pass, naming the damaged shard
 of one `{key}.ec` directory and healing it by hashing the one rebuilt shard
-(storage.cpp), beside mxec_scrub_object.
+(storage_scrub.cpp), beside mxec_scrub_object.
 
 Objects are written with put_object_chunked at the reference's own test
 shape (350 B in 100-byte chunks: 4 + 2) and at 20 000-byte chunks (five data

@@ -1,5 +1,5 @@
 """GPU: mxec_scrub_object -- the scrub / heal call over one `{key}.ec`
-directory (storage.cpp), which the reference does not have (SURVEY.md §3.2,
+directory (storage_scrub.cpp), which the reference does not have (SURVEY.md §3.2,
 §5: no scrubber, no heal-on-read, no background repair).
 
 Objects are written with put_object_chunked: five data chunks with a short
