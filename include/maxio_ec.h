@@ -565,7 +565,13 @@ int mxec_frames_decrypt(mxec_ctx* ctx, const uint8_t key[32], uint64_t first_ind
                         const uint8_t* aad, uint32_t aad_len, uint32_t frame_size,
                         const uint8_t* frames, uint64_t frames_len, uint64_t plaintext_size,
                         uint8_t* out, uint64_t out_cap, uint64_t* out_len);
-/* Device-resident batches: one launch over every frame of every job. */
+/* Device-resident batches: one launch over every frame of every job.
+ * Pointer contract: in_dev, out_dev and aad_dev may have any byte alignment.
+ * A payload sits 12 bytes into its frame and frames are frame_size + 28 bytes
+ * apart, so the two sides of a copy are never 16-byte aligned together; the
+ * kernel declares no alignment on its 16-byte accesses and gfx950 serves
+ * global memory unaligned.  Nothing is rejected for its alignment.  The
+ * buffers of one call must not overlap.                                      */
 typedef struct mxec_frames_job {
     const uint8_t* key;       /* host, 32 bytes */
     uint8_t nonce_prefix[4];  /* encrypt only */

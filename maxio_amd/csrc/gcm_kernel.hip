@@ -204,15 +204,19 @@ __device__ __forceinline__ uint32_t mask_be(uint32_t n, uint32_t q) {
     return c >= 4 ? 0xFFFFFFFFu : c <= 0 ? 0u : ~(0xFFFFFFFFu >> (8 * c));
 }
 
-// 16 bytes at a 4-byte aligned address (frame payloads sit 12 bytes into a
-// frame) as big-endian words.
-typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+// 16 bytes at any address as big-endian words.  A payload sits 12 bytes into
+// its frame and a caller's frame stream starts where it likes
+// (include/maxio_ec.h: no alignment asked of in_dev / out_dev), so the type
+// claims none.  gfx950 under amdhsa runs global memory in unaligned access
+// mode: this is one dwordx4 access whatever the address, the same
+// instruction the compiler makes of the header's and the tag's byte loops.
+typedef uint32_t u32x4a1 __attribute__((ext_vector_type(4), aligned(1)));
 __device__ __forceinline__ u32x4 load16_be(const uint8_t* p) {
-    const u32x4a4 v = *reinterpret_cast<const u32x4a4*>(p);
+    const u32x4a1 v = *reinterpret_cast<const u32x4a1*>(p);
     return u32x4{bswap(v.x), bswap(v.y), bswap(v.z), bswap(v.w)};
 }
 __device__ __forceinline__ void store16_be(uint8_t* p, u32x4 v) {
-    *reinterpret_cast<u32x4a4*>(p) = u32x4a4{bswap(v.x), bswap(v.y), bswap(v.z), bswap(v.w)};
+    *reinterpret_cast<u32x4a1*>(p) = u32x4a1{bswap(v.x), bswap(v.y), bswap(v.z), bswap(v.w)};
 }
 
 // LDS: the four T-tables replicated 32 times, laid out so that a lookup's

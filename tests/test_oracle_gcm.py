@@ -7,6 +7,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+import gcm_cases
 import openssl_gcm
 import oracle
 
@@ -78,6 +79,66 @@ def test_frames_layout_and_round_trip(n):
         assert fr[12:12 + ln] == ct and fr[12 + ln:12 + ln + 16] == tag
     rc, back = oracle.frames_decrypt(key, out, n, aads)
     assert rc == 0 and back == pt
+
+
+def _check_job_against_openssl(job):
+    """Every frame of job: the header, the ciphertext and tag as OpenSSL
+    gives them for that nonce, and the way back."""
+    out = oracle.frames_encrypt(job.key, job.prefix, job.pt, **job.oracle_args())
+    assert len(out) == job.frames_len, job.label
+    for f, (fo, po, ln, index) in enumerate(gcm_cases.frame_slices(job)):
+        fr = out[fo:fo + 12 + ln + 16]
+        assert fr[:12] == job.prefix + index.to_bytes(8, "little"), (job.label, f)
+        ct, tag = openssl_gcm.encrypt(job.key, fr[:12], job.pt[po:po + ln], job.aads[f] if job.aads else b"")
+        assert fr[12:12 + ln] == ct, (job.label, f, "ciphertext")
+        assert fr[12 + ln:] == tag, (job.label, f, "tag")
+    rc, back = oracle.frames_decrypt(job.key, out, len(job.pt), **job.oracle_args())
+    assert rc == 0 and back == job.pt, job.label
+
+
+@needs_openssl
+def test_lane_and_stream_cases_match_openssl():
+    """The GPU sweep's own frames (gcm_cases.py): indices up to 2^64 - 1, AADs
+    of 0 .. 4101 bytes with partial last blocks, block counts on both sides
+    of every multiple of 256 up to 769."""
+    jobs = gcm_cases.lane_cases() + gcm_cases.stream_cases()
+    assert {j.aad_len for j in jobs} >= set(gcm_cases.AAD_LENS)
+    assert {j.first_index for j in jobs} >= set(gcm_cases.INDICES)
+    for job in jobs:
+        _check_job_against_openssl(job)
+
+
+@needs_openssl
+def test_tiny_cases_match_openssl():
+    for job in gcm_cases.tiny_cases(300):
+        _check_job_against_openssl(job)
+
+
+@needs_openssl
+def test_counter_boundary_frame_matches_openssl():
+    """One frame of 65534 blocks: the last counter is 0xFFFF."""
+    job = gcm_cases.counter_edge_case()
+    assert job.n_frames == 2 and job.frame_size == 65534 * 16
+    _check_job_against_openssl(job)
+
+
+def test_case_table_shape():
+    """The table holds what the sweep relies on: every (na, m, last block)
+    combination, single frames, and the byte-equal keys in two buffers."""
+    lane = gcm_cases.lane_cases()
+    assert all(j.n_frames == 1 and j.frame_size == 16384 for j in lane)
+    seen = {((j.aad_len + 15) // 16, (j.aad_len + 15) // 16 + (len(j.pt) + 15) // 16 + 1, len(j.pt) % 16 or 16)
+            for j in lane}
+    for na in (0, 1, 2, 3, 255, 256, 257):
+        for m in gcm_cases.SEQ_LENS:
+            if m - na - 1 >= 1:
+                assert {(na, m, t) for t in (16, 1, 15)} <= seen, (na, m)
+    keys = {id(j.key): j.key for j in lane}
+    assert len(keys) == 8 and len(set(keys.values())) == 7
+    assert all(any(b & 0x80 for b in j.prefix) for j in lane)
+    tiny = gcm_cases.tiny_cases(300)
+    assert len({j.key for j in tiny}) == 23 and all(1 <= len(j.pt) <= 600 and j.n_frames == 1 for j in tiny)
+    assert [j.n_frames for j in gcm_cases.stream_cases()] == [3, 11, 2300]
 
 
 def test_frames_errors():
