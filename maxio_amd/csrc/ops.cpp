@@ -1,4 +1,5 @@
-// ops.cpp — descriptor planning and kernel launches over device pointers.
+// ops.cpp — kernel launches over device pointers: the RS launches planned by
+// rs_plan.hpp, the grid tuner, the coefficient lookups, the SHA-256 launches.
 #include <cstdlib>
 #include <cstring>
 
@@ -6,12 +7,10 @@
 
 #include <algorithm>
 #include <climits>
-#include <deque>
 #include <cstring>
 #include <map>
 
 #include "kernels.hpp"
-#include "locate_plan.hpp"
 #include "sha_plan.hpp"
 
 namespace mxec {
@@ -124,83 +123,30 @@ int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, i
         }
         MXEC_TRY(affinity_check(dev, &slot, s, "run_rs", arena, ps.data(), ps.size()));
     }
-    DescWriter w(slot, arena);
-    const uint64_t tile = rs_tile_bytes(rs_default_variant(uint32_t(r)));
-    const uint64_t tiles_per_obj = (shard_size + tile - 1) / tile;
-    bool aligned = true;
-    for (size_t o = 0; o < n && aligned; ++o) {
-        for (int j = 0; j < k; ++j) aligned &= (reinterpret_cast<uintptr_t>(objs[o].in[j]) & 15) == 0;
-        for (int i = 0; i < r; ++i) aligned &= (reinterpret_cast<uintptr_t>(objs[o].out[i]) & 15) == 0;
-    }
     // Aligned launches handle length boundaries inside the fast kernel; an
     // unaligned pointer sends every tile to the byte-exact edge kernel.
-    std::vector<uint64_t> edges;
-    if (!aligned)
-        for (size_t o = 0; o < n; ++o)
-            for (uint64_t t = 0; t < tiles_per_obj; ++t) edges.push_back(uint64_t(o) << 32 | t);
-    const size_t o_in = w.add(sizeof(void*) * n * k);
-    const size_t o_out = w.add(sizeof(void*) * n * r);
-    const size_t o_inlen = w.add(8 * n * k);
-    const size_t o_outlen = w.add(8 * n * r);
-    const size_t o_coef = w.add(4 * n);
-    const size_t o_edge = w.add(8 * edges.size());
-    const bool locate = objs[0].locate != nullptr;  // r = m in 2..8: one row block
-    const bool verify = objs[0].first_bad != nullptr || locate;
-    const size_t o_fb = verify ? w.add(sizeof(void*) * n) : 0;
-    const size_t o_lf = locate ? w.add(kLocateFieldBytes) : 0;
-    const size_t o_lt = locate ? w.add(locate_table_bytes(r)) : 0;
-    const size_t o_lo = locate ? w.add(4 * n) : 0;  // zero: one table
-    char* hb = w.data();
+    bool aligned = true;
+    for (size_t o = 0; o < n && aligned; ++o) aligned = rs_aligned(objs[o], k, r);
+    const RsPass pass = rs_pass_of(objs[0]);
+    const bool locate = pass == kRsLocate;  // r = m in 2..8: one row block
+    const bool verify = pass != kRsStore;
+    RsTable t = RsTable::uniform(n, k, r, shard_size, rs_tile_bytes(rs_default_variant(uint32_t(r))), aligned, pass);
     if (locate) {
         if (r < 2 || r > 8) return set_error(MXEC_E_INVALID_ARG, "locate needs 2..8 parity rows");
-        locate_field_tables(reinterpret_cast<uint8_t*>(hb + o_lf));
-        MXEC_TRY(locate_table(k, r, reinterpret_cast<uint8_t*>(hb + o_lt)));
+        t.locate_k(k);  // one table, every object's offset zero
     }
-    auto** ip = reinterpret_cast<const uint8_t**>(hb + o_in);
-    auto** op = reinterpret_cast<uint8_t**>(hb + o_out);
-    auto* il = reinterpret_cast<uint64_t*>(hb + o_inlen);
-    auto* ol = reinterpret_cast<uint64_t*>(hb + o_outlen);
-    auto* co = reinterpret_cast<uint32_t*>(hb + o_coef);
-    for (size_t o = 0; o < n; ++o) {
-        const RsObject& ob = objs[o];
-        for (int j = 0; j < k; ++j) {
-            ip[o * k + j] = ob.in[j];
-            il[o * k + j] = std::min<uint64_t>(ob.in_len[j], shard_size);
-        }
-        for (int i = 0; i < r; ++i) {
-            op[o * r + i] = ob.out[i];
-            ol[o * r + i] = std::min<uint64_t>(ob.out_len[i], shard_size);
-        }
-        co[o] = ob.coef_off;
-        if (verify) reinterpret_cast<void**>(hb + o_fb)[o] = locate ? ob.locate : static_cast<void*>(ob.first_bad);
-    }
-    if (!edges.empty()) std::memcpy(hb + o_edge, edges.data(), 8 * edges.size());
+    DescWriter w(slot, arena);
+    t.lay(w, true);
+    char* hb = w.data();
+    if (locate) MXEC_TRY(rs_locate_fill(hb, &t, 1, locate_table));
+    for (const RsObject& ob : objs) t.put(hb, ob, k, r, shard_size);
     char* db = nullptr;
     MXEC_TRY(w.commit(s, &db));
-    RsArgs a{};
-    a.in_ptrs = reinterpret_cast<const uint8_t* const*>(db + o_in);
-    a.out_ptrs = reinterpret_cast<uint8_t* const*>(db + o_out);
-    a.in_len = reinterpret_cast<const uint64_t*>(db + o_inlen);
-    a.out_len = reinterpret_cast<const uint64_t*>(db + o_outlen);
+    RsArgs a = t.args(db);
     a.coef = static_cast<const uint32_t*>(dev.coef.p);
-    a.coef_off = reinterpret_cast<const uint32_t*>(db + o_coef);
-    a.edge_list = reinterpret_cast<const uint64_t*>(db + o_edge);
-    a.n_edge = edges.size();
-    a.edge_tile_bytes = tile;
     a.shard_size = shard_size;
-    a.n_obj = uint32_t(n);
     a.k = uint32_t(k);
-    a.r_total = uint32_t(r);
-    a.aligned = aligned ? 1u : 0u;
     a.max_blocks = max_blocks ? max_blocks : dev.kn ? dev.kn->test_rs_grid : 0u;
-    if (locate) {
-        a.locate = reinterpret_cast<LocateRec* const*>(db + o_fb);
-        a.loc_field = reinterpret_cast<const uint8_t*>(db + o_lf);
-        a.loc_tab = reinterpret_cast<const uint8_t*>(db + o_lt);
-        a.loc_off = reinterpret_cast<const uint32_t*>(db + o_lo);
-    } else if (verify) {
-        a.first_bad = reinterpret_cast<uint64_t* const*>(db + o_fb);
-    }
     if (max_blocks || verify) tune = false;  // the tuner times encodes and decodes only
     // Large aligned single-launch batches take the grid tuner's pick.
     GridTuner::Trial trial;
@@ -350,231 +296,62 @@ void rs_grid_release(Device& dev) {
 
 int run_rs_mixed(Device& dev, Slot& slot, hipStream_t s, const std::map<int, std::vector<RsMixedObject>>& groups,
                  DescArena* arena, uint32_t cap) {
-    // Which groups take the grouped kernel: every pointer 16-byte aligned,
-    // r <= 8, index ranges that fit its 32-bit fields.  A call that is one
-    // uniform group keeps the uniform kernel (no tile table).
-    struct Plan {
-        int r = 0;
-        const std::vector<RsMixedObject>* objs = nullptr;
-        uint64_t sum_k = 0, n_tiles = 0, tile = 0;
-        size_t o_in = 0, o_out = 0, o_inlen = 0, o_outlen = 0, o_coef = 0, o_tiles = 0, o_fb = 0;
-        size_t o_lt = 0, o_lo = 0;            // locate: the group's (k, m) tables, each object's offset
-        std::map<int, uint32_t> loc_of_k;     // k -> byte offset within o_lt
-    };
-    std::vector<Plan> grouped;
-    std::vector<std::pair<int, const std::vector<RsMixedObject>*>> rest;
-    // Per r: the aligned objects (grouped launch) and the others (per (k, S)
-    // launches through run_rs, whose edge kernel takes unaligned pointers).
-    std::deque<std::vector<RsMixedObject>> parts;
-    for (const auto& g : groups) {
-        const int r = g.first;
-        if (g.second.empty() || r == 0) continue;
-        auto& al = parts.emplace_back();
-        auto& un = parts.emplace_back();
-        for (const RsMixedObject& ob : g.second) {
-            bool aligned = r <= 8;
-            for (int j = 0; j < ob.k && aligned; ++j) aligned &= (reinterpret_cast<uintptr_t>(ob.o.in[j]) & 15) == 0;
-            for (int i = 0; i < r && aligned; ++i) aligned &= (reinterpret_cast<uintptr_t>(ob.o.out[i]) & 15) == 0;
-            (aligned ? al : un).push_back(ob);
+    // Verify and locate hold for every object of a call or none (RsObject).
+    RsPass pass = kRsStore;
+    for (const auto& g : groups)
+        if (!g.second.empty()) {
+            pass = rs_pass_of(g.second[0].o);
+            break;
         }
-        if (!un.empty()) rest.emplace_back(r, &un);
-        if (al.empty()) continue;
-        bool uniform = true;
-        Plan p;
-        p.r = r;
-        p.objs = &al;
-        p.tile = rs_tile_bytes(rs_group_variant(uint32_t(r)));
-        for (const RsMixedObject& ob : al) {
-            uniform &= ob.k == al[0].k && ob.shard_size == al[0].shard_size;
-            p.sum_k += uint64_t(ob.k);
-            p.n_tiles += (ob.shard_size + p.tile - 1) / p.tile;
-        }
-        const bool fits = al.size() <= UINT32_MAX && p.sum_k <= UINT32_MAX && p.n_tiles <= (uint64_t(1) << 32);
-        if (fits && !(uniform && groups.size() == 1 && un.empty())) grouped.push_back(p);
-        else rest.emplace_back(r, &al);
-    }
-    for (const auto& g : rest) {
-        // One launch per (k, shard_size), in order of first appearance.
-        std::map<std::pair<int, uint64_t>, std::vector<RsObject>> by;
-        std::vector<std::pair<int, uint64_t>> order;
-        for (const RsMixedObject& ob : *g.second) {
-            auto key = std::make_pair(ob.k, ob.shard_size);
-            auto& v = by[key];
-            if (v.empty()) order.push_back(key);
-            v.push_back(ob.o);
-        }
-        for (const auto& key : order)
-            MXEC_TRY(run_rs(dev, slot, s, key.second, key.first, g.first, by[key], arena, true, cap));
-    }
-    if (grouped.empty()) return MXEC_OK;
+    const bool locate = pass == kRsLocate;
+    // Which objects take grouped launches, which one run_rs per (k, shard
+    // size), and whether the grouped launches fuse into one multi-r launch
+    // (rs_plan.hpp; MXEC_RS_MULTI=0 keeps one launch per r).
+    const uint64_t m_tile = rs_tile_bytes(rs_group_variant(kMultiR));
+    const RsMixedPlan plan = rs_plan_mixed(
+        groups, [](int r) { return rs_tile_bytes(rs_group_variant(uint32_t(r))); }, m_tile,
+        !dev.kn || dev.kn->rs_multi, pass != kRsStore);
+    for (const RsMixedPlan::Rest& u : plan.rest)
+        MXEC_TRY(run_rs(dev, slot, s, u.shard_size, u.k, u.r, u.objs, arena, true, cap));
+    if (plan.grouped.empty()) return MXEC_OK;
     if (affinity_on(dev)) {
         std::vector<const void*> ps;
-        for (const Plan& p : grouped)
-            for (const RsMixedObject& ob : *p.objs) {
+        for (const RsMixedPlan::Group& g : plan.grouped)
+            for (const RsMixedObject& ob : g.objs) {
                 for (int j = 0; j < ob.k; ++j) ps.push_back(ob.o.in[j]);
-                for (int i = 0; i < p.r; ++i) ps.push_back(ob.o.out[i]);
+                for (int i = 0; i < g.r; ++i) ps.push_back(ob.o.out[i]);
             }
         MXEC_TRY(affinity_check(dev, &slot, s, "run_rs_mixed", arena, ps.data(), ps.size()));
     }
-    // Two or more grouped launches of r <= kMultiR with the same tile: one
-    // multi-r launch instead (rs_apply_multi; MXEC_RS_MULTI=0 keeps one
-    // launch per r).
-    // A verify call (RsObject::first_bad) runs one launch per r.
-    const bool locate = (*grouped[0].objs)[0].o.locate != nullptr;
-    const bool verify = (*grouped[0].objs)[0].o.first_bad != nullptr || locate;
-    const bool multi_on = !verify && (!dev.kn || dev.kn->rs_multi);
-    const uint32_t max_blocks = cap ? cap : dev.kn ? dev.kn->test_rs_grid : 0u;
-    bool multi = multi_on && grouped.size() >= 2;
-    uint64_t m_obj = 0, m_k = 0, m_tiles = 0;
-    const uint64_t m_tile = rs_tile_bytes(rs_group_variant(kMultiR));
-    for (const Plan& p : grouped) {
-        multi = multi && p.r <= int(kMultiR) && p.tile == m_tile;
-        m_obj += p.objs->size();
-        m_k += p.sum_k;
-        m_tiles += p.n_tiles;
-    }
-    multi = multi && m_obj <= UINT32_MAX / kMultiR && m_k <= UINT32_MAX && m_tiles <= (uint64_t(1) << 32);
-    if (multi) {
-        DescWriter w(slot, arena);
-        const size_t o_in = w.add(sizeof(void*) * m_k);
-        const size_t o_out = w.add(sizeof(void*) * m_obj * kMultiR);
-        const size_t o_inlen = w.add(8 * m_k);
-        const size_t o_outlen = w.add(8 * m_obj * kMultiR);  // zero: unused output entries
-        const size_t o_coef = w.add(4 * m_obj);
-        const size_t o_tiles = w.add(sizeof(RsTileRec) * m_tiles);
-        char* hb = w.data();
-        auto** ip = reinterpret_cast<const uint8_t**>(hb + o_in);
-        auto** op = reinterpret_cast<uint8_t**>(hb + o_out);
-        auto* il = reinterpret_cast<uint64_t*>(hb + o_inlen);
-        auto* ol = reinterpret_cast<uint64_t*>(hb + o_outlen);
-        auto* co = reinterpret_cast<uint32_t*>(hb + o_coef);
-        auto* tr = reinterpret_cast<RsTileRec*>(hb + o_tiles);
-        uint64_t o = 0, in0 = 0, t0 = 0;
-        for (const Plan& p : grouped) {
-            for (const RsMixedObject& ob : *p.objs) {
-                for (int j = 0; j < ob.k; ++j) {
-                    ip[in0 + j] = ob.o.in[j];
-                    il[in0 + j] = std::min<uint64_t>(ob.o.in_len[j], ob.shard_size);
-                }
-                for (int i = 0; i < p.r; ++i) {
-                    op[o * kMultiR + i] = ob.o.out[i];
-                    ol[o * kMultiR + i] = std::min<uint64_t>(ob.o.out_len[i], ob.shard_size);
-                }
-                co[o] = ob.o.coef_off;
-                const uint64_t nt = (ob.shard_size + m_tile - 1) / m_tile;
-                const uint32_t kr = uint32_t(ob.k) | uint32_t(p.r) << 16;
-                for (uint64_t t = 0; t < nt; ++t) tr[t0 + t] = RsTileRec{uint32_t(o), kr, uint32_t(in0), uint32_t(t)};
-                in0 += uint64_t(ob.k);
-                t0 += nt;
-                ++o;
-            }
-        }
-        char* db = nullptr;
-        MXEC_TRY(w.commit(s, &db));
-        RsArgs a{};
-        a.in_ptrs = reinterpret_cast<const uint8_t* const*>(db + o_in);
-        a.out_ptrs = reinterpret_cast<uint8_t* const*>(db + o_out);
-        a.in_len = reinterpret_cast<const uint64_t*>(db + o_inlen);
-        a.out_len = reinterpret_cast<const uint64_t*>(db + o_outlen);
-        a.coef = static_cast<const uint32_t*>(dev.coef.p);
-        a.coef_off = reinterpret_cast<const uint32_t*>(db + o_coef);
-        a.n_obj = uint32_t(m_obj);
-        a.r = a.r_total = kMultiR;
-        a.row0 = 0;
-        a.aligned = 1;
-        a.multi = 1;
-        a.tiles = reinterpret_cast<const RsTileRec*>(db + o_tiles);
-        a.n_tiles = m_tiles;
-        a.max_blocks = max_blocks;
-        MXEC_HIP(launch_rs_apply(a, dev.n_cus, s));
-        return w.finish(s);
+    // One table per launch: the multi-r launch's over every group, or one
+    // per grouped launch.
+    std::vector<RsTable> ts;
+    if (plan.multi) ts.push_back(RsTable::grouped(plan.m_obj, plan.m_k, plan.m_tiles, kMultiR, m_tile, pass, true));
+    for (const RsMixedPlan::Group& g : plan.grouped) {
+        if (plan.multi) break;  // never a verify or a locate
+        ts.push_back(RsTable::grouped(g.objs.size(), g.sum_k, g.n_tiles, uint32_t(g.r), g.tile, pass));
+        if (!locate) continue;
+        if (g.r < 2 || g.r > 8) return set_error(MXEC_E_INVALID_ARG, "locate needs 2..8 parity rows");
+        for (const RsMixedObject& ob : g.objs) ts.back().locate_k(ob.k);
     }
     // Every grouped launch's tables in one upload: one host-to-device copy
     // ahead of the launches instead of one between each pair of them (a
     // copy in the stream costs ~25-50 us of idle GPU at that point).
     DescWriter w(slot, arena);
-    for (Plan& p : grouped) {
-        const size_t n = p.objs->size();
-        p.o_in = w.add(sizeof(void*) * p.sum_k);
-        p.o_out = w.add(sizeof(void*) * n * p.r);
-        p.o_inlen = w.add(8 * p.sum_k);
-        p.o_outlen = w.add(8 * n * p.r);
-        p.o_coef = w.add(4 * n);
-        p.o_tiles = w.add(sizeof(RsTileRec) * p.n_tiles);
-        if (verify) p.o_fb = w.add(sizeof(void*) * n);
-        if (locate) {
-            if (p.r < 2 || p.r > 8) return set_error(MXEC_E_INVALID_ARG, "locate needs 2..8 parity rows");
-            for (const RsMixedObject& ob : *p.objs)
-                if (!p.loc_of_k.count(ob.k)) {
-                    const uint32_t at = uint32_t(p.loc_of_k.size()) * locate_table_bytes(p.r);
-                    p.loc_of_k.emplace(ob.k, at);
-                }
-            p.o_lt = w.add(p.loc_of_k.size() * locate_table_bytes(p.r));
-            p.o_lo = w.add(4 * n);
-        }
-    }
+    for (RsTable& t : ts) t.lay(w, false);
     const size_t o_lf = locate ? w.add(kLocateFieldBytes) : 0;
+    for (RsTable& t : ts) t.o_lf = o_lf;
     char* hb = w.data();
-    if (locate) {
-        locate_field_tables(reinterpret_cast<uint8_t*>(hb + o_lf));
-        for (const Plan& p : grouped)
-            for (const auto& kt : p.loc_of_k)
-                MXEC_TRY(locate_table(kt.first, p.r, reinterpret_cast<uint8_t*>(hb + p.o_lt + kt.second)));
-    }
-    for (const Plan& p : grouped) {
-        const int r = p.r;
-        auto** ip = reinterpret_cast<const uint8_t**>(hb + p.o_in);
-        auto** op = reinterpret_cast<uint8_t**>(hb + p.o_out);
-        auto* il = reinterpret_cast<uint64_t*>(hb + p.o_inlen);
-        auto* ol = reinterpret_cast<uint64_t*>(hb + p.o_outlen);
-        auto* co = reinterpret_cast<uint32_t*>(hb + p.o_coef);
-        auto* tr = reinterpret_cast<RsTileRec*>(hb + p.o_tiles);
-        uint64_t in0 = 0, t0 = 0;
-        for (size_t o = 0; o < p.objs->size(); ++o) {
-            const RsMixedObject& ob = (*p.objs)[o];
-            for (int j = 0; j < ob.k; ++j) {
-                ip[in0 + j] = ob.o.in[j];
-                il[in0 + j] = std::min<uint64_t>(ob.o.in_len[j], ob.shard_size);
-            }
-            for (int i = 0; i < r; ++i) {
-                op[o * r + i] = ob.o.out[i];
-                ol[o * r + i] = std::min<uint64_t>(ob.o.out_len[i], ob.shard_size);
-            }
-            co[o] = ob.o.coef_off;
-            if (verify) reinterpret_cast<void**>(hb + p.o_fb)[o] = locate ? ob.o.locate : static_cast<void*>(ob.o.first_bad);
-            if (locate) reinterpret_cast<uint32_t*>(hb + p.o_lo)[o] = p.loc_of_k.at(ob.k);
-            const uint64_t nt = (ob.shard_size + p.tile - 1) / p.tile;
-            for (uint64_t t = 0; t < nt; ++t)
-                tr[t0 + t] = RsTileRec{uint32_t(o), uint32_t(ob.k), uint32_t(in0), uint32_t(t)};
-            in0 += uint64_t(ob.k);
-            t0 += nt;
-        }
-    }
+    if (locate) MXEC_TRY(rs_locate_fill(hb, ts.data(), ts.size(), locate_table));
+    for (size_t i = 0; i < plan.grouped.size(); ++i)
+        for (const RsMixedObject& ob : plan.grouped[i].objs)
+            ts[plan.multi ? 0 : i].put(hb, ob.o, ob.k, plan.grouped[i].r, ob.shard_size);
     char* db = nullptr;
     MXEC_TRY(w.commit(s, &db));
-    for (const Plan& p : grouped) {
-        RsArgs a{};
-        a.in_ptrs = reinterpret_cast<const uint8_t* const*>(db + p.o_in);
-        a.out_ptrs = reinterpret_cast<uint8_t* const*>(db + p.o_out);
-        a.in_len = reinterpret_cast<const uint64_t*>(db + p.o_inlen);
-        a.out_len = reinterpret_cast<const uint64_t*>(db + p.o_outlen);
+    for (const RsTable& t : ts) {
+        RsArgs a = t.args(db);
         a.coef = static_cast<const uint32_t*>(dev.coef.p);
-        a.coef_off = reinterpret_cast<const uint32_t*>(db + p.o_coef);
-        a.n_obj = uint32_t(p.objs->size());
-        a.r = a.r_total = uint32_t(p.r);
-        a.row0 = 0;
-        a.aligned = 1;
-        a.tiles = reinterpret_cast<const RsTileRec*>(db + p.o_tiles);
-        a.n_tiles = p.n_tiles;
-        a.max_blocks = max_blocks;
-        if (locate) {
-            a.locate = reinterpret_cast<LocateRec* const*>(db + p.o_fb);
-            a.loc_field = reinterpret_cast<const uint8_t*>(db + o_lf);
-            a.loc_tab = reinterpret_cast<const uint8_t*>(db + p.o_lt);
-            a.loc_off = reinterpret_cast<const uint32_t*>(db + p.o_lo);
-        } else if (verify) {
-            a.first_bad = reinterpret_cast<uint64_t* const*>(db + p.o_fb);
-        }
+        a.max_blocks = cap ? cap : dev.kn ? dev.kn->test_rs_grid : 0u;
         MXEC_HIP(launch_rs_apply(a, dev.n_cus, s));
     }
     return w.finish(s);

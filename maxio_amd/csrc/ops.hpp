@@ -12,32 +12,13 @@
 #include <vector>
 
 #include "gf256.hpp"
+#include "rs_plan.hpp"
 #include "runtime.hpp"
 
 namespace mxec {
 
-
-// One object of an RS launch: k inputs -> r outputs, device pointers.
-struct RsObject {
-    const uint8_t* const* in;  // k
-    const uint64_t* in_len;    // k
-    uint8_t* const* out;       // r
-    const uint64_t* out_len;   // r
-    uint32_t coef_off;         // dword offset of this object's [j][i][8] table
-    // Verify (ReedSolomon::verify) when set, for every object of the call or
-    // none: `out` are the stored parity rows, read and compared with the
-    // recomputed ones, never written; first_bad (device, r entries, filled
-    // with 0xFF on the stream ahead of the call) receives per row the lowest
-    // byte offset at which they differ (kernels.hpp RsArgs::first_bad).
-    uint64_t* first_bad = nullptr;
-    // Locate (mxec_locate) when set instead, again for every object of the
-    // call or none: the verify's launch with r = m in 2..8 rows, but a
-    // mismatch is classified and folded into this device record (a
-    // LocateRec, kernels.hpp; initialised with launch_locate_init on the
-    // stream ahead of the call).  The launch uploads the (k, m) tables of
-    // locate_plan.hpp with its descriptor tables.
-    void* locate = nullptr;
-};
+// RsObject and RsMixedObject, what run_rs and run_rs_mixed take: rs_plan.hpp,
+// with the host-only plan of their launches and descriptor tables.
 
 // Applies each object's matrix; all objects share (k, r, shard_size).
 // arena: take the descriptor tables from it instead of the slot's ring (many
@@ -60,12 +41,6 @@ void rs_grid_record(Device& dev, int k, int r, uint64_t shard_size, const GridTu
 int rs_grid_in_use(Device& dev, int k, int r, uint64_t shard_size);
 void rs_grid_release(Device& dev);
 
-// An object of a mixed batch: its own k and shard size.
-struct RsMixedObject {
-    int k;
-    uint64_t shard_size;
-    RsObject o;
-};
 // Applies each object's matrix, objects grouped by r (map key).  Per r, the
 // objects whose pointers are all 16-byte aligned (r <= 8) share one grouped
 // launch (rs_apply_fast<GRP>), every grouped launch's tables in one upload;

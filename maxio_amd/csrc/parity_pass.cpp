@@ -49,7 +49,7 @@ int queue_init(const Pass& ps, uint64_t bytes, hipStream_t s) {
     return MXEC_OK;
 }
 
-// `parity` is written under Store and only read otherwise (ops.hpp RsObject).
+// `parity` is written under Store and only read otherwise (rs_plan.hpp RsObject).
 RsObject rs_object(const Pass& ps, const uint8_t* const* in, const uint8_t* const* parity, const uint64_t* len, int k,
                    uint32_t coef_off, uint64_t result_off) {
     RsObject ob{in, len, const_cast<uint8_t* const*>(parity), len + k, coef_off};

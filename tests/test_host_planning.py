@@ -10,7 +10,12 @@
 * the piece grid of the piece-major host waves tiles every message with
   and without a ramp and after widening mid-wave (piece_grid.hpp);
 * the wave cutter of the host batch calls keeps every object in exactly one
-  wave, in order, within the pool allowance unless alone (wave_cut.hpp)."""
+  wave, in order, within the pool allowance unless alone (wave_cut.hpp);
+* the Reed-Solomon launch planner lays out the descriptor tables of the
+  uniform, unaligned, grouped, verify / locate and multi-r launches so that a
+  walk of each launch meets every (object, tile) once on that object's
+  entries, and splits a mixed call into grouped, uniform and multi-r launches
+  by its alignment, uniformity and 32-bit rules (rs_plan.hpp)."""
 from __future__ import annotations
 
 import os
@@ -25,7 +30,8 @@ HERE = os.path.join(ROOT, "tests", "c_manifest")
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 @pytest.mark.parametrize("src,ok", [("sha_guard_check.cpp", "sha guard ok"), ("deal_check.cpp", "deal ok"),
-                                    ("piece_grid_check.cpp", "piece grid ok"), ("wave_cut_check.cpp", "wave cut ok")])
+                                    ("piece_grid_check.cpp", "piece grid ok"), ("wave_cut_check.cpp", "wave cut ok"),
+                                    ("rs_plan_check.cpp", "rs plan ok")])
 def test_host_planning(tmp_path, src, ok):
     exe = str(tmp_path / src.split(".")[0])
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",

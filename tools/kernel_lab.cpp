@@ -17,6 +17,7 @@
 
 #include "../maxio_amd/csrc/gf256.hpp"
 #include "../maxio_amd/csrc/kernels.hpp"
+#include "../maxio_amd/csrc/rs_plan.hpp"
 
 #define CK(x)                                                                          \
     do {                                                                               \
@@ -210,8 +211,7 @@ struct Batch {
     Batch(const uint8_t* data, uint8_t* par, Shape sh, const std::vector<uint32_t>& table, uint32_t** coef_dev) {
         std::vector<const uint8_t*> ip(sh.n * sh.k);
         std::vector<uint8_t*> op(sh.n * sh.r);
-        std::vector<uint64_t> il(sh.n * sh.k, sh.S), ol(sh.n * sh.r, sh.S);
-        std::vector<uint32_t> co(sh.n, 0);
+        const std::vector<uint64_t> len(size_t(std::max(sh.k, sh.r)), sh.S);
         // MXEC_LAB_OM=1: the bench's object-major layout ([n][k+r][S + pad],
         // pad 2 MiB + 64 KiB for multi-MiB shards) from `data`; else data
         // [n][k][S] and parity [n][r][S] apart.
@@ -224,26 +224,21 @@ struct Batch {
                 op[o * sh.r + i] = om ? const_cast<uint8_t*>(data) + (o * (sh.k + sh.r) + sh.k + i) * ss
                                       : par + (o * sh.r + i) * sh.S;
         }
-        size_t bytes = ip.size() * 8 + op.size() * 8 + il.size() * 8 + ol.size() * 8 + co.size() * 4 + 64;
-        CK(hipMalloc(&mem, bytes));
-        char* p = static_cast<char*>(mem);
-        auto put = [&](const void* src, size_t n) { CK(hipMemcpy(p, src, n, hipMemcpyHostToDevice)); char* r = p; p += (n + 15) & ~size_t(15); return r; };
-        a.in_ptrs = reinterpret_cast<const uint8_t* const*>(put(ip.data(), ip.size() * 8));
-        a.out_ptrs = reinterpret_cast<uint8_t* const*>(put(op.data(), op.size() * 8));
-        a.in_len = reinterpret_cast<const uint64_t*>(put(il.data(), il.size() * 8));
-        a.out_len = reinterpret_cast<const uint64_t*>(put(ol.data(), ol.size() * 8));
-        a.coef_off = reinterpret_cast<const uint32_t*>(put(co.data(), co.size() * 4));
+        // The library's own table builder (rs_plan.hpp), every pointer aligned.
+        const uint64_t tile = mxec::rs_tile_bytes(mxec::rs_default_variant(uint32_t(sh.r)));
+        mxec::RsTable t = mxec::RsTable::uniform(sh.n, sh.k, sh.r, sh.S, tile, true, mxec::kRsStore);
+        mxec::RsImage img;
+        t.lay(img, true);
+        for (uint64_t o = 0; o < sh.n; ++o)
+            t.put(img.data(), mxec::RsObject{&ip[o * sh.k], len.data(), &op[o * sh.r], len.data(), 0}, sh.k, sh.r, sh.S);
+        CK(hipMalloc(&mem, img.v.size()));
+        CK(hipMemcpy(mem, img.data(), img.v.size(), hipMemcpyHostToDevice));
+        a = t.args(static_cast<char*>(mem));
         CK(hipMalloc(coef_dev, table.size() * 4));
         CK(hipMemcpy(*coef_dev, table.data(), table.size() * 4, hipMemcpyHostToDevice));
         a.coef = *coef_dev;
         a.shard_size = sh.S;
-        a.n_edge = 0;
-        a.n_obj = uint32_t(sh.n);
         a.k = uint32_t(sh.k);
-        a.r = uint32_t(sh.r);
-        a.r_total = uint32_t(sh.r);
-        a.row0 = 0;
-        a.aligned = 1;
     }
     ~Batch() { (void)hipFree(mem); }
 };
