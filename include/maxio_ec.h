@@ -295,6 +295,30 @@ int mxec_encode_strided_device(mxec_ctx* ctx, int dev, void* stream, int k,
                                uint64_t parity_shard_stride,
                                uint8_t* digests_dev);
 
+/* Running parity over a window of the data shards (a streaming PUT folds
+ * chunks in as they arrive; the crate computes parity only once every chunk
+ * is on disk, filesystem.rs:1121-1124, so this call replaces nothing in it):
+ * parity_out = parity_in ^ M(k,m)[:, first .. first+count) * data window, per
+ * object.  data points at shard `first` of object 0 (only the window need be
+ * resident); data_len: host, `count` entries, NULL = shard_size.  parity_in
+ * NULL: zeros (the first window).  parity_in and parity_out must not overlap
+ * (MXEC_E_INVALID_ARG): the pass reads one and writes the other, never one
+ * buffer in place.  Enqueue-only.  After windows that together cover [0, k)
+ * exactly once, in any order, parity_out holds mxec_encode_strided_device's
+ * parity.  Each update moves (count + 2m) * shard_size bytes per object.
+ * (k, m) and shard-size errors are mxec_encode_strided_device's; first < 0,
+ * count < 1, first + count > k, a null data or parity_out and overlapping
+ * in / out rows are MXEC_E_INVALID_ARG, all decided before anything is
+ * enqueued. */
+int mxec_encode_update_strided_device(mxec_ctx* ctx, int dev, void* stream, int k,
+                                      int m, uint64_t shard_size, uint64_t n_obj,
+                                      int first, int count, const uint8_t* data,
+                                      uint64_t data_obj_stride, uint64_t data_shard_stride,
+                                      const uint64_t* data_len, const uint8_t* parity_in,
+                                      uint64_t in_obj_stride, uint64_t in_shard_stride,
+                                      uint8_t* parity_out, uint64_t out_obj_stride,
+                                      uint64_t out_shard_stride);
+
 /* General batch: object o has k[o] data and m[o] parity shards of
  * shard_size[o] bytes; the pointer arrays are host arrays of device pointers,
  * concatenated over objects (sum k, sum m entries); data_len likewise (NULL =
@@ -673,6 +697,58 @@ int mxec_complete_multipart_chunked_encrypted(mxec_ctx* ctx, const char* ec_dir,
                                               const uint8_t* aad_prefix, uint32_t aad_prefix_len,
                                               char etag_out[48]);
 
+/* put_object_chunked (filesystem.rs:686-773) as a push stream: the body is
+ * written in pieces of any size and never buffered whole -- the write-side
+ * counterpart of mxec_reader_*.  The handle is an opaque `mxec_writer`, passed
+ * as void* (as mxec_scrub_object passes its report).
+ *
+ * mxec_writer_open (filesystem.rs:686-708): total_len is the body's length,
+ * declared up front (Content-Length, x-amz-decoded-content-length, or the sum
+ * of a multipart upload's parts): k = ceil(total_len / chunk_size), 1 for an
+ * empty body, and the encoding matrix depends on k.  plaintext_size:
+ * UINT64_MAX, or manifest.plaintext_size (a caller streaming an
+ * encrypt-then-EC frame stream).  window_bytes: HBM for data chunks in
+ * flight, 0 = default (4 chunks); at least 2 * chunk_size is used.  One device
+ * of the context is chosen here, round robin, and kept.  chunk_size == 0 is
+ * MXEC_E_INVALID_ARG; k + m > 255 with parity is MXEC_E_TOO_MANY_SHARDS_255
+ * with put_object_chunked's text.  Unlike the reference, which writes every
+ * data chunk before compute_and_write_parity hits that guard, both fail here
+ * and nothing is created: k is known before the first byte.
+ *
+ * mxec_writer_write (filesystem.rs:709-737): any len, any split; returns once
+ * buf is reusable.  Bytes go to the chunk's file ({index:06}) and to the
+ * chunk's slot of the HBM window; a completed chunk's SHA-256 and its fold
+ * into the running parity (mxec_encode_update_strided_device, count = 1) are
+ * queued and the call returns.  It waits for the GPU only when the window is
+ * full: the oldest chunk's hash or parity pass has not finished.
+ *
+ * mxec_writer_finish (filesystem.rs:738-773): takes exactly total_len bytes
+ * written (else MXEC_E_INVALID_ARG "body ended at X of Y declared bytes"),
+ * drains, writes the parity files, then manifest.json last.  ec_dir then
+ * holds exactly the files and manifest bytes mxec_put_object_chunked writes
+ * for the concatenated body, however it was split.
+ *
+ * mxec_writer_close: always; without a finish no manifest exists and the
+ * chunk files written so far are left.
+ *
+ * Errors poison the writer: writing past total_len (MXEC_E_INVALID_ARG), an
+ * I/O or device error, a short finish -- every later write or finish returns
+ * that error and no manifest is ever written.
+ * Memory: host, two page-locked staging pieces of at most 1 MiB each (body
+ * bytes on their way up, parity rows on their way down to their files) and
+ * the manifest's entries, one digest per chunk; HBM, the window plus
+ * 2 * m * chunk_size.  No buffer of either grows with total_len or holds more
+ * than a piece of a chunk on the host.
+ * Threads: one writer is used by one thread at a time; any number of writers
+ * run concurrently on a context, each on a stream of its own, sharing a slot
+ * lock only within a call. */
+typedef struct mxec_writer mxec_writer;
+int mxec_writer_open(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size,
+                     uint32_t parity_shards, uint64_t total_len, uint64_t plaintext_size,
+                     uint64_t window_bytes, void** out);
+int mxec_writer_write(void* w, const uint8_t* buf, uint64_t len);
+int mxec_writer_finish(void* w);
+void mxec_writer_close(void* w);
 
 /* GET of a whole EC object (VerifiedChunkReader over manifest.json,
  * chunk_reader.rs:35-152): verified chunks, RS recovery of bad ones.

@@ -156,6 +156,8 @@ _SIGS = {
     "mxec_reconstruct": (INT, [P, INT, INT, SZ, PP, SZP, U8P, U8P, ctypes.c_uint32, ctypes.POINTER(INT)]),
     "mxec_encode_strided_device": (
         INT, [P, INT, P, INT, INT, U64, U64, P, U64, U64, U64P, P, U64, U64, P]),
+    "mxec_encode_update_strided_device": (
+        INT, [P, INT, P, INT, INT, U64, U64, INT, INT, P, U64, U64, U64P, P, U64, U64, P, U64, U64]),
     "mxec_encode_batch_device": (INT, [P, INT, P, ctypes.POINTER(Object), U64, PP, U64P, PP, P]),
     "mxec_verify": (INT, [P, INT, INT, SZ, PP, SZP, PP, U64P, ctypes.POINTER(INT)]),
     "mxec_verify_strided_device": (
@@ -203,6 +205,11 @@ _SIGS = {
     "mxec_get_object_chunked_encrypted": (INT, [P, ctypes.c_char_p, P, P, ctypes.c_uint32, ctypes.c_uint32, U64,
                                                 U64, U64, P, U64, U64P]),
     "mxec_try_reconstruct_data_chunk": (INT, [P, ctypes.c_char_p, ctypes.c_uint32, P, U64, U64P]),
+    "mxec_writer_open": (INT, [P, ctypes.c_char_p, U64, ctypes.c_uint32, U64, U64, U64,
+                               ctypes.POINTER(ctypes.c_void_p)]),
+    "mxec_writer_write": (INT, [P, P, U64]),
+    "mxec_writer_finish": (INT, [P]),
+    "mxec_writer_close": (None, [P]),
     "mxec_reader_open": (INT, [P, ctypes.c_char_p, U64, U64, U64, ctypes.POINTER(ctypes.c_void_p)]),
     "mxec_reader_read": (ctypes.c_int64, [P, P, U64]),
     "mxec_reader_close": (None, [P]),

@@ -15,12 +15,14 @@
 
 namespace mxec {
 
+int too_many_shards(uint64_t k, uint64_t m) {
+    return set_error(MXEC_E_TOO_MANY_SHARDS_255,
+                     "too many shards: " + std::to_string(k) + " data + " + std::to_string(m) + " parity = " +
+                         std::to_string(k + m) + " > 255 (GF(2^8) limit). Increase --chunk-size");
+}
+
 int check_km(int k, int m) {
-    if (k + m > 255)
-        return set_error(MXEC_E_TOO_MANY_SHARDS_255,
-                         "too many shards: " + std::to_string(k) + " data + " + std::to_string(m) +
-                             " parity = " + std::to_string(k + m) +
-                             " > 255 (GF(2^8) limit). Increase --chunk-size");
+    if (k + m > 255) return too_many_shards(uint64_t(k), uint64_t(m));
     int rc = rs_check(k, m);
     if (rc) return set_error(rc, std::string("Reed-Solomon init error: ") + mxec_strerror(rc));
     return MXEC_OK;
@@ -120,6 +122,7 @@ int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, i
         for (const RsObject& ob : objs) {
             for (int j = 0; j < k; ++j) ps.push_back(ob.in[j]);
             for (int i = 0; i < r; ++i) ps.push_back(ob.out[i]);
+            for (int i = 0; i < r && ob.seed; ++i) ps.push_back(ob.seed[i]);
         }
         MXEC_TRY(affinity_check(dev, &slot, s, "run_rs", arena, ps.data(), ps.size()));
     }
@@ -131,6 +134,14 @@ int run_rs(Device& dev, Slot& slot, hipStream_t s, uint64_t shard_size, int k, i
     const bool locate = pass == kRsLocate;  // r = m in 2..8: one row block
     const bool verify = pass != kRsStore;
     RsTable t = RsTable::uniform(n, k, r, shard_size, rs_tile_bytes(rs_default_variant(uint32_t(r))), aligned, pass);
+    // A seeded store (every object or none, RsObject::seed): the encode's
+    // launch from seed rows.  Its k is a window's, so the tuner neither
+    // times it nor lends it a grid.
+    t.seeded = objs[0].seed != nullptr;
+    for (const RsObject& ob : objs)
+        if ((ob.seed != nullptr) != t.seeded || (t.seeded && verify))
+            return set_error(MXEC_E_INVALID_ARG, "a seed is for every object of a store launch or none");
+    if (t.seeded) tune = false;
     if (locate) {
         if (r < 2 || r > 8) return set_error(MXEC_E_INVALID_ARG, "locate needs 2..8 parity rows");
         t.locate_k(k);  // one table, every object's offset zero

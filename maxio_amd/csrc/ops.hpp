@@ -184,6 +184,8 @@ int pipe_open(Device& dev);
 
 // filesystem.rs:1095 guard, then the crate's ReedSolomon::new checks.
 int check_km(int k, int m);
+// The guard's error (MXEC_E_TOO_MANY_SHARDS_255) with the reference's text.
+int too_many_shards(uint64_t k, uint64_t m);
 
 // chunk_reader.rs:203-206's error text for an object short of k shards.
 inline std::string too_few_msg(int present, int k, int total) {

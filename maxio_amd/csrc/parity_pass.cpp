@@ -2,6 +2,8 @@
 // object's m parity rows from its k data shards, then store them (encode),
 // compare them with the stored rows (verify) or classify the mismatches
 // (locate); each from host pointers, a strided device batch or a mixed one.
+// The strided encode also runs over a window of the data shards from a
+// running parity (mxec_encode_update_strided_device).
 #include <algorithm>
 
 #include "../../include/maxio_ec.h"
@@ -26,6 +28,9 @@ namespace {
 enum class Policy { Store, Compare, Locate };
 struct Pass { Policy p; void* result = nullptr; };  // device memory in the two bodies, the caller's in host_pass
 struct Strided { const uint8_t* base; uint64_t obj_stride, shard_stride; };
+// A window of a Store pass: data shards [first, first + count) of the k, the
+// data base at shard `first`, folded into the rows at `seed` (null base: zeros).
+struct Window { int first, count; Strided seed; };
 
 // Bytes of result that `objs` objects with `rows` parity rows in all occupy.
 uint64_t result_bytes(Policy p, uint64_t objs, uint64_t rows) {
@@ -61,16 +66,25 @@ RsObject rs_object(const Pass& ps, const uint8_t* const* in, const uint8_t* cons
 
 // The uniform body: n_obj objects of one (k, m, shard_size) and one table of
 // k + m shard lengths.  digests_dev (Store only, or null): every shard's SHA-256.
+// win (Store only, or null): the launch has the window's `count` inputs (len:
+// count + m entries) and reads the (k, m) table from column `first` on -- its
+// layout is [j][i][8], so a column range is contiguous.
 int uniform_pass(Device& d, Slot& slot, hipStream_t s, const Pass& ps, int k, int m, uint64_t shard_size,
-                 uint64_t n_obj, Strided data, Strided parity, const std::vector<uint64_t>& len, uint8_t* digests_dev) {
-    const int total = k + m;
-    std::vector<const uint8_t*> sh(static_cast<size_t>(n_obj * total));  // per object: k data, m parity
+                 uint64_t n_obj, Strided data, Strided parity, const std::vector<uint64_t>& len, uint8_t* digests_dev,
+                 const Window* win = nullptr) {
+    const int kin = win ? win->count : k, total = kin + m;
+    const bool seeded = win && win->seed.base;
+    std::vector<const uint8_t*> sh(static_cast<size_t>(n_obj * total));  // per object: kin data, m parity
+    std::vector<const uint8_t*> seeds(seeded ? static_cast<size_t>(n_obj * m) : 0);
     std::vector<RsObject> objs(static_cast<size_t>(n_obj));
     for (uint64_t o = 0; o < n_obj; ++o) {
         const uint8_t** p = &sh[o * total];
-        for (int j = 0; j < k; ++j) p[j] = data.base + o * data.obj_stride + j * data.shard_stride;
-        for (int i = 0; i < m; ++i) p[k + i] = parity.base + o * parity.obj_stride + i * parity.shard_stride;
-        objs[o] = rs_object(ps, p, p + k, len.data(), k, 0, result_bytes(ps.p, o, o * m));
+        for (int j = 0; j < kin; ++j) p[j] = data.base + o * data.obj_stride + j * data.shard_stride;
+        for (int i = 0; i < m; ++i) p[kin + i] = parity.base + o * parity.obj_stride + i * parity.shard_stride;
+        objs[o] = rs_object(ps, p, p + kin, len.data(), kin, 0, result_bytes(ps.p, o, o * m));
+        for (int i = 0; i < m && seeded; ++i)
+            seeds[o * m + i] = win->seed.base + o * win->seed.obj_stride + i * win->seed.shard_stride;
+        if (seeded) objs[o].seed = &seeds[o * m];
     }
     uint32_t off = 0;
     MXEC_TRY(with_stable_coef(d, s, [&] { return encode_coef(d, k, m, &off); }, [&] {
@@ -78,27 +92,53 @@ int uniform_pass(Device& d, Slot& slot, hipStream_t s, const Pass& ps, int k, in
         // table recycle (with_stable_coef) starts from clean entries, so
         // first_bad and n_bad are those of one pass.
         MXEC_TRY(queue_init(ps, result_bytes(ps.p, n_obj, n_obj * m), s));
-        for (auto& ob : objs) ob.coef_off = off;
-        return run_rs(d, slot, s, shard_size, k, m, objs);
+        for (auto& ob : objs) ob.coef_off = off + (win ? uint32_t(win->first) * uint32_t(m) * 8u : 0u);
+        return run_rs(d, slot, s, shard_size, kin, m, objs);
     }));
     std::vector<uint64_t> lens;
     for (uint64_t o = 0; o < n_obj && digests_dev; ++o) lens.insert(lens.end(), len.begin(), len.end());
     return digests_dev ? run_sha(d, slot, s, sh, lens, digests_dev, nullptr, nullptr) : MXEC_OK;
 }
 
+// Whether any seed row shares a byte with any row written.
+bool rows_overlap(const Strided& a, const Strided& b, uint64_t n_obj, int m, uint64_t shard_size) {
+    std::vector<std::pair<uintptr_t, int>> at;  // row starts: 0 = a, 1 = b
+    for (uint64_t o = 0; o < n_obj; ++o)
+        for (int i = 0; i < m; ++i) {
+            at.emplace_back(reinterpret_cast<uintptr_t>(a.base) + o * a.obj_stride + i * a.shard_stride, 0);
+            at.emplace_back(reinterpret_cast<uintptr_t>(b.base) + o * b.obj_stride + i * b.shard_stride, 1);
+        }
+    std::sort(at.begin(), at.end());
+    uintptr_t end[2] = {0, 0};  // how far the rows of each side seen so far reach
+    for (const auto& r : at) {
+        if (r.first < end[1 - r.second]) return true;
+        end[r.second] = std::max(end[r.second], r.first + uintptr_t(shard_size));
+    }
+    return false;
+}
+
 int strided_pass(const Pass& ps, mxec_ctx* ctx, int dev, void* stream, int k, int m, uint64_t shard_size,
-                 uint64_t n_obj, Strided data, const uint64_t* data_len, Strided parity, uint8_t* digests_dev) {
+                 uint64_t n_obj, Strided data, const uint64_t* data_len, Strided parity, uint8_t* digests_dev,
+                 const Window* win = nullptr) {
     return guarded([&] {
         MXEC_TRY(check_shape(ps.p, k, m, shard_size));
+        if (win && (win->first < 0 || win->count < 1 || win->first > k - win->count))
+            return set_error(MXEC_E_INVALID_ARG, "window [" + std::to_string(win->first) + ", +" +
+                                                     std::to_string(win->count) + ") is not within the " +
+                                                     std::to_string(k) + " data shards");
+        if (win && (!data.base || !parity.base)) return set_error(MXEC_E_INVALID_ARG, "null base pointer");
+        if (win && win->seed.base && rows_overlap(win->seed, parity, n_obj, m, shard_size))
+            return set_error(MXEC_E_INVALID_ARG, "parity_in and parity_out overlap");
         if (n_obj == 0) return MXEC_OK;
         if (!data.base || !parity.base) return set_error(MXEC_E_INVALID_ARG, "null base pointer");
         if (ps.p != Policy::Store && !ps.result) return set_error(MXEC_E_INVALID_ARG, "null result array");
         DevScope ds;
         MXEC_TRY(ds.open(ctx, dev));
-        std::vector<uint64_t> len(static_cast<size_t>(k + m), shard_size);
-        for (int j = 0; j < k && data_len; ++j) len[size_t(j)] = std::min<uint64_t>(data_len[j], shard_size);
+        const int kin = win ? win->count : k;
+        std::vector<uint64_t> len(static_cast<size_t>(kin + m), shard_size);
+        for (int j = 0; j < kin && data_len; ++j) len[size_t(j)] = std::min<uint64_t>(data_len[j], shard_size);
         hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-        return uniform_pass(*ds.d, *ds.slot, s, ps, k, m, shard_size, n_obj, data, parity, len, digests_dev);
+        return uniform_pass(*ds.d, *ds.slot, s, ps, k, m, shard_size, n_obj, data, parity, len, digests_dev, win);
     });
 }
 
@@ -237,6 +277,17 @@ int mxec_encode_strided_device(mxec_ctx* ctx, int dev, void* stream, int k, int 
     return strided_pass({Policy::Store}, ctx, dev, stream, k, m, shard_size, n_obj,
                         {data, data_obj_stride, data_shard_stride}, data_len,
                         {parity, parity_obj_stride, parity_shard_stride}, digests_dev);
+}
+
+int mxec_encode_update_strided_device(mxec_ctx* ctx, int dev, void* stream, int k, int m, uint64_t shard_size,
+                                      uint64_t n_obj, int first, int count, const uint8_t* data,
+                                      uint64_t data_obj_stride, uint64_t data_shard_stride, const uint64_t* data_len,
+                                      const uint8_t* parity_in, uint64_t in_obj_stride, uint64_t in_shard_stride,
+                                      uint8_t* parity_out, uint64_t out_obj_stride, uint64_t out_shard_stride) {
+    const Window win{first, count, {parity_in, in_obj_stride, in_shard_stride}};
+    return strided_pass({Policy::Store}, ctx, dev, stream, k, m, shard_size, n_obj,
+                        {data, data_obj_stride, data_shard_stride}, data_len,
+                        {parity_out, out_obj_stride, out_shard_stride}, nullptr, &win);
 }
 
 int mxec_verify_strided_device(mxec_ctx* ctx, int dev, void* stream, int k, int m, uint64_t shard_size,

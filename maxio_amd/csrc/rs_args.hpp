@@ -81,6 +81,17 @@ struct RsArgs {
     const uint8_t* loc_field = nullptr;
     const uint8_t* loc_tab = nullptr;
     const uint32_t* loc_off = nullptr;
+    // Seeded launch (mxec_encode_update_strided_device) when set: a uniform
+    // store launch whose accumulators start from seed rows instead of zero,
+    // out = seed ^ coef * in.  [n_obj][r_total] like out_ptrs, read at
+    // [row0, row0 + r) and cut at out_len like the rows written.  nullptr is
+    // the plain launch, bit for bit.  The seed rows and the output rows are
+    // different buffers, by contract: with_stable_coef (ops.hpp) may queue a
+    // batch again over the same outputs and relies on the kernels reading only
+    // inputs and writing only outputs -- a read-modify-write of one buffer
+    // would fold the window in twice.  Reading seed_ptrs and writing out_ptrs,
+    // a re-run is exact.  Not with tiles, first_bad or locate.
+    const uint8_t* const* seed_ptrs = nullptr;
 };
 constexpr uint32_t kMultiR = 4;
 

@@ -34,6 +34,9 @@
 //    all r syndromes stored ^ recomputed, one ballot per tile; only a wave
 //    that finds a mismatch goes on to name the shard each bad byte column
 //    points at.
+//  * mxec_encode_update_strided_device is the encode with the accumulators
+//    loaded from seed rows instead of zeroed (the kSeed policy, rs_update_*):
+//    out = seed ^ M[:, window] * window, (count + 2r) x S bytes of traffic.
 #include "kernels.hpp"
 
 #include <cstdlib>
@@ -222,8 +225,9 @@ __device__ __forceinline__ void report_first_bad(uint64_t* const* __restrict__ f
 // What a tile does with its accumulators: the encode / decode stores them,
 // the verify compares them with the stored rows (report_first_bad), the
 // locate forms every row's syndrome and, on a mismatch, classifies each bad
-// byte column (below).
-enum : int { kStore = 0, kCmp = 1, kLocate = 2 };
+// byte column (below).  kSeed is kStore whose accumulators start from the
+// object's seed rows (RsArgs::seed_ptrs) instead of zero.
+enum : int { kStore = 0, kCmp = 1, kLocate = 2, kSeed = 3 };
 
 // Locate launches (RsArgs::locate set).  The walk, the loads and the masks
 // are the verify's; a wave whose syndromes are all zero (every wave of a
@@ -331,7 +335,8 @@ __device__ __forceinline__ void edge_step(
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint64_t shard_size,
     uint32_t k, uint32_t r_total, uint32_t row0, const uint64_t* __restrict__ edge_list,
     uint32_t steps_per_tile, uint64_t tile_bytes, uint32_t aligned, uint64_t step,
-    uint64_t* const* __restrict__ fb_ptrs = nullptr, LocArgs loc = {}) {
+    uint64_t* const* __restrict__ fb_ptrs = nullptr, LocArgs loc = {},
+    const uint8_t* const* __restrict__ seed_ptrs = nullptr) {
     const uint64_t e = edge_list[step / steps_per_tile];
     const uint32_t obj = uint32_t(e >> 32);
     const uint64_t col = uint64_t(uint32_t(e)) * tile_bytes + (step % steps_per_tile) * kEdgeTile +
@@ -347,10 +352,24 @@ __device__ __forceinline__ void edge_step(
     }
     const uint32_t* __restrict__ tab = coef + coef_off[obj] + row0 * 8;
     uint32_t acc[1][4][R];
+    if constexpr (POL == kSeed) {
+        // The seed rows below their length, as the stores below cut the rows written.
 #pragma unroll
-    for (int w = 0; w < 4; ++w)
+        for (int i = 0; i < R; ++i) {
+            uint64_t olen = out_len[uint64_t(obj) * r_total + row0 + i];
+            if (olen > shard_size) olen = shard_size;
+            const int64_t valid = col < olen ? int64_t(olen - col) : 0;
+            Vec4 sd{{0, 0, 0, 0}};
+            if (valid > 0) sd = load_partial(seed_ptrs[uint64_t(obj) * r_total + row0 + i] + col, valid, aligned != 0);
 #pragma unroll
-        for (int i = 0; i < R; ++i) acc[0][w][i] = 0;
+            for (int w = 0; w < 4; ++w) acc[0][w][i] = sd.w[w];
+        }
+    } else {
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+#pragma unroll
+            for (int i = 0; i < R; ++i) acc[0][w][i] = 0;
+    }
     // Four inputs' loads in flight before their multiply-accumulates.
     // Whole vectors load unconditionally from a global address (a safe
     // dummy when the lane's vector is not whole) so the waits stay
@@ -469,6 +488,20 @@ __global__ __launch_bounds__(kThreads) void rs_verify_edge(
                            edge_list, steps_per_tile, tile_bytes, aligned, step, fb_ptrs);
 }
 
+// The encode's walk from seed rows (a seeded launch).
+template <int R>
+__global__ __launch_bounds__(kThreads) void rs_update_edge(
+    const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
+    const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
+    const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint64_t shard_size,
+    uint32_t k, uint32_t r_total, uint32_t row0, const uint64_t* __restrict__ edge_list,
+    uint32_t steps_per_tile, uint64_t tile_bytes, uint32_t aligned, uint64_t n_steps,
+    const uint8_t* const* __restrict__ seed_ptrs) {
+    for (uint64_t step = blockIdx.x; step < n_steps; step += gridDim.x)
+        edge_step<R, kSeed>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, shard_size, k, r_total, row0,
+                            edge_list, steps_per_tile, tile_bytes, aligned, step, nullptr, {}, seed_ptrs);
+}
+
 // And for a locate launch.
 template <int R>
 __global__ __launch_bounds__(kThreads) void rs_locate_edge(
@@ -499,25 +532,56 @@ __device__ __forceinline__ Vec4 gload16_upto(gcptr p, int32_t valid, gcptr safe)
 // first_bad pointer, `row` is the index of its first row there.  kLocate
 // (locate launches): the stored rows loaded and cut the same way, then every
 // row's syndrome at once; loc.rec / loc.off point at the object's entries.
+// kSeed (seeded launches): sp are the object's R seed rows, loaded into the
+// accumulators ahead of the first input block (so both are in flight
+// together) and cut at ol like the stored rows of a verify; then the encode.
 template <int R, int V, int POL = kStore>
 __device__ __forceinline__ void rs_tile(const uint8_t* const* __restrict__ ip, const uint64_t* __restrict__ il,
                                         uint8_t* const* __restrict__ op, const uint64_t* __restrict__ ol,
                                         const uint32_t* __restrict__ tab, uint32_t k, uint32_t stride,
                                         uint64_t base, gcptr safe, uint64_t* const* __restrict__ fbp = nullptr,
-                                        uint32_t row = 0, LocArgs loc = {}) {
-    constexpr bool CMP = POL != kStore;  // the stored rows are read, nothing is written
+                                        uint32_t row = 0, LocArgs loc = {},
+                                        const uint8_t* const* __restrict__ sp = nullptr) {
+    constexpr bool CMP = POL == kCmp || POL == kLocate;  // the stored rows are read, nothing is written
     constexpr uint32_t kTile = kThreads * 16 * V;
     const uint64_t end = base + kTile;
     const uint64_t lane = base + threadIdx.x * 16;
     const int32_t lane_off = int32_t(threadIdx.x * 16);
 
     uint32_t acc[V][4][R];
+    if constexpr (POL == kSeed) {
+        // A row that ends at or before the tile seeds nothing; the
+        // straddling vector is masked at the row's length.
 #pragma unroll
-    for (int v = 0; v < V; ++v)
+        for (int i = 0; i < R; ++i) {
+            const uint64_t olen = ol[i];
+            gcptr q = ((gcptr)(sp[i])) + lane;
+            Vec4 sd[V];
+            if (olen >= end) {
 #pragma unroll
-        for (int w = 0; w < 4; ++w)
+                for (int v = 0; v < V; ++v) sd[v] = gload16(q + v * kThreads * 16);
+            } else if (olen <= base) {
 #pragma unroll
-            for (int i = 0; i < R; ++i) acc[v][w][i] = 0;
+                for (int v = 0; v < V; ++v) sd[v] = Vec4{{0, 0, 0, 0}};
+            } else {
+                const int32_t d = int32_t(olen - base) - lane_off;
+#pragma unroll
+                for (int v = 0; v < V; ++v)
+                    sd[v] = gload16_upto(q + v * kThreads * 16, d - v * int32_t(kThreads * 16), safe);
+            }
+#pragma unroll
+            for (int v = 0; v < V; ++v)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) acc[v][w][i] = sd[v].w[w];
+        }
+    } else {
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+#pragma unroll
+                for (int i = 0; i < R; ++i) acc[v][w][i] = 0;
+    }
 
     // Input jj of a group: whole (the common case), zero, or cut.
     auto load_in = [&](uint32_t jj, Vec4 (&x)[V]) {
@@ -689,7 +753,8 @@ __device__ __forceinline__ void fast_tiles(
     const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
     const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
     uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
-    const RsTileRec* __restrict__ tiles, uint64_t* const* __restrict__ fb_ptrs, LocArgs loc = {}) {
+    const RsTileRec* __restrict__ tiles, uint64_t* const* __restrict__ fb_ptrs, LocArgs loc = {},
+    const uint8_t* const* __restrict__ seed_ptrs = nullptr) {
     constexpr uint32_t kTile = kThreads * 16 * V;
     const gcptr safe = (gcptr)(reinterpret_cast<const uint8_t*>(coef));
     RsTileRec next{};
@@ -719,7 +784,8 @@ __device__ __forceinline__ void fast_tiles(
         }
         rs_tile<R, V, POL>(in_ptrs + in0, in_len + in0, out_ptrs + uint64_t(obj) * r_total + row0,
                            out_len + uint64_t(obj) * r_total + row0, coef + coef_off[obj] + row0 * 8, k, r_total, base,
-                           safe, POL == kCmp ? fb_ptrs + obj : nullptr, row0, lo);
+                           safe, POL == kCmp ? fb_ptrs + obj : nullptr, row0, lo,
+                           POL == kSeed ? seed_ptrs + uint64_t(obj) * r_total + row0 : nullptr);
     }
 }
 
@@ -747,6 +813,20 @@ __global__ __launch_bounds__(kThreads) void rs_verify_fast(
     const RsTileRec* __restrict__ tiles, uint64_t* const* __restrict__ fb_ptrs) {
     fast_tiles<R, V, GRP, kCmp>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform, r_total, row0,
                                 tiles_per_obj, n_tiles, tiles, fb_ptrs);
+}
+
+// The seeded encode (rs_tile kSeed): out = seed ^ coef * in.  seed_ptrs are
+// laid out like out_ptrs and never name the rows written.  Uniform launches
+// only.  Reads (k + r) x S bytes per object and writes r x S.
+template <int R, int V>
+__global__ __launch_bounds__(kThreads) void rs_update_fast(
+    const uint8_t* const* __restrict__ in_ptrs, uint8_t* const* __restrict__ out_ptrs,
+    const uint64_t* __restrict__ in_len, const uint64_t* __restrict__ out_len,
+    const uint32_t* __restrict__ coef, const uint32_t* __restrict__ coef_off, uint32_t k_uniform,
+    uint32_t r_total, uint32_t row0, uint32_t tiles_per_obj, uint64_t n_tiles,
+    const uint8_t* const* __restrict__ seed_ptrs) {
+    fast_tiles<R, V, false, kSeed>(in_ptrs, out_ptrs, in_len, out_len, coef, coef_off, k_uniform, r_total, row0,
+                                   tiles_per_obj, n_tiles, nullptr, nullptr, {}, seed_ptrs);
 }
 
 // mxec_locate: the verify's geometry and walk with the locate policy
@@ -813,6 +893,16 @@ LocArgs loc_args(const RsArgs& a) { return LocArgs{a.locate, a.loc_field, a.loc_
 template <int R, int V, bool GRP>
 hipError_t launch_fast(const RsArgs& a, uint32_t tiles_per_obj, uint64_t n_tiles, uint64_t blocks,
                        hipStream_t s) {
+    if (a.seed_ptrs) {
+        if constexpr (!GRP) {
+            if (a.first_bad) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((rs_update_fast<R, V>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
+                               a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
+                               tiles_per_obj, n_tiles, a.seed_ptrs);
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;  // grouped launches take no seed
+    }
     if (a.first_bad)
         hipLaunchKernelGGL((rs_verify_fast<R, V, GRP>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s, a.in_ptrs,
                            a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off, a.k, a.r_total, a.row0,
@@ -859,6 +949,7 @@ hipError_t launch_grouped(const RsArgs& a, int n_cus, hipStream_t s) {
 template <int R>
 hipError_t launch_r(const RsArgs& a, int n_cus, hipStream_t s, const RsVariant& var) {
     const uint64_t tile = rs_tile_bytes(var);
+    if (a.seed_ptrs && (a.locate || a.first_bad)) return hipErrorInvalidValue;
     if (a.aligned) {  // cut tiles run inside the fast kernel; no edge list
         const uint32_t tiles_per_obj = uint32_t((a.shard_size + tile - 1) / tile);
         const uint64_t n_tiles = uint64_t(tiles_per_obj) * a.n_obj;
@@ -893,6 +984,13 @@ hipError_t launch_r(const RsArgs& a, int n_cus, hipStream_t s, const RsVariant& 
                                a.in_ptrs, a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off,
                                a.shard_size, a.k, a.r_total, a.row0, a.edge_list, steps, tile, a.aligned,
                                n_steps, a.first_bad);
+            return hipGetLastError();
+        }
+        if (a.seed_ptrs) {
+            hipLaunchKernelGGL((rs_update_edge<R>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s,
+                               a.in_ptrs, a.out_ptrs, a.in_len, a.out_len, a.coef, a.coef_off,
+                               a.shard_size, a.k, a.r_total, a.row0, a.edge_list, steps, tile, a.aligned,
+                               n_steps, a.seed_ptrs);
             return hipGetLastError();
         }
         hipLaunchKernelGGL((rs_apply_edge<R>), dim3(uint32_t(blocks)), dim3(kThreads), 0, s,
@@ -980,6 +1078,7 @@ hipError_t launch_locate_init(LocateRec* recs, uint64_t n, hipStream_t s) {
 }
 
 hipError_t launch_rs_apply(const RsArgs& a, int n_cus, hipStream_t s) {
+    if (a.tiles && a.seed_ptrs) return hipErrorInvalidValue;  // uniform launches only
     if (a.tiles && a.multi) {
         if (!a.aligned || a.row0 != 0 || a.first_bad || a.locate) return hipErrorInvalidValue;  // no multi-r verify
         if (a.n_tiles == 0) return hipSuccess;

@@ -39,6 +39,10 @@ struct RsObject {
     // stream ahead of the call).  The launch uploads the (k, m) tables of
     // locate_plan.hpp with its descriptor tables.
     void* locate = nullptr;
+    // Seeded store (uniform launches only, every object of the call or none):
+    // r rows the accumulators start from instead of zero, read below out_len
+    // like the rows written; never the rows of `out` (RsArgs::seed_ptrs).
+    const uint8_t* const* seed = nullptr;
 };
 
 // An object of a mixed batch: its own k and shard size.
@@ -54,6 +58,7 @@ inline bool rs_aligned(const RsObject& ob, int k, int r) {
     uintptr_t bits = 0;
     for (int j = 0; j < k; ++j) bits |= reinterpret_cast<uintptr_t>(ob.in[j]);
     for (int i = 0; i < r; ++i) bits |= reinterpret_cast<uintptr_t>(ob.out[i]);
+    for (int i = 0; i < r && ob.seed; ++i) bits |= reinterpret_cast<uintptr_t>(ob.seed[i]);
     return (bits & 15) == 0;
 }
 
@@ -77,10 +82,12 @@ struct RsTable {
     bool aligned = true;           // uniform: false sends every tile to the edge list
     uint64_t n_list = 0;           // tile records (tiled) or edge entries (unaligned), else 0
     RsPass pass = kRsStore;
+    bool seeded = false;           // uniform store: a seed row per output entry (set before lay)
     std::map<int, uint32_t> loc_of_k;  // locate: k -> byte offset of its (k, r) table within o_lt
 
     size_t o_in = 0, o_out = 0, o_inlen = 0, o_outlen = 0, o_coef = 0, o_list = 0, o_res = 0;
     size_t o_lf = 0, o_lt = 0, o_lo = 0;  // locate: field block, (k, r) tables, each object's offset
+    size_t o_seed = 0;                    // seeded: [n_obj][r] seed rows, behind every other section
     uint64_t o = 0, in0 = 0, t0 = 0;      // put()'s next object, input entry and list entry
 
     // Objects of any k and shard size: n_in input entries and n_tiles tiles
@@ -118,6 +125,7 @@ struct RsTable {
         o_coef = w.add(4 * n_obj);
         o_list = w.add((tiled ? sizeof(RsTileRec) : 8) * n_list);
         if (pass != kRsStore) o_res = w.add(sizeof(void*) * n_obj);
+        if (seeded) o_seed = w.add(sizeof(void*) * n_obj * r);
         if (pass != kRsLocate) return;
         if (own_field) o_lf = w.add(kLocateFieldBytes);
         o_lt = w.add(loc_of_k.size() * locate_table_bytes(int(r)));
@@ -141,6 +149,8 @@ struct RsTable {
             ol[i] = std::min<uint64_t>(ob.out_len[i], shard_size);
         }
         reinterpret_cast<uint32_t*>(hb + o_coef)[obj] = ob.coef_off;
+        if (seeded)
+            for (int i = 0; i < r_obj; ++i) (reinterpret_cast<const uint8_t**>(hb + o_seed) + obj * r)[i] = ob.seed[i];
         if (pass != kRsStore)
             reinterpret_cast<void**>(hb + o_res)[obj] = pass == kRsLocate ? ob.locate : static_cast<void*>(ob.first_bad);
         if (pass == kRsLocate) reinterpret_cast<uint32_t*>(hb + o_lo)[obj] = loc_of_k.at(k);
@@ -186,6 +196,7 @@ struct RsTable {
         } else if (pass == kRsVerify) {
             a.first_bad = reinterpret_cast<uint64_t* const*>(db + o_res);
         }
+        if (seeded) a.seed_ptrs = reinterpret_cast<const uint8_t* const*>(db + o_seed);
         return a;
     }
 };

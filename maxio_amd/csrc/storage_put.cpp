@@ -27,12 +27,6 @@ void fill_info(mxec_chunk_info* ci, uint32_t index, uint64_t size, const uint8_t
     ci->kind = kind;
 }
 
-int too_many_shards(int k, int m) {
-    return set_error(MXEC_E_TOO_MANY_SHARDS_255,
-                     "too many shards: " + std::to_string(k) + " data + " + std::to_string(m) + " parity = " +
-                         std::to_string(k + m) + " > 255 (GF(2^8) limit). Increase --chunk-size");
-}
-
 // m parity shards of chunk_size bytes for the k data chunks (the encode
 // writes every byte: no zero-fill) and the k+m digests.
 int encode_parity(mxec_ctx* ctx, uint64_t chunk_size, const std::vector<const uint8_t*>& dp,

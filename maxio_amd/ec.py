@@ -457,6 +457,18 @@ class Context:
             data_shard_stride, _u64p(data_len) if data_len is not None else None, parity_ptr,
             parity_obj_stride, parity_shard_stride, digests_ptr))
 
+    def encode_update_strided_device(self, k, m, shard_size, n_obj, first, count, data_ptr, data_obj_stride,
+                                     data_shard_stride, parity_in_ptr, in_obj_stride, in_shard_stride,
+                                     parity_out_ptr, out_obj_stride, out_shard_stride, data_len=None, dev=0,
+                                     stream=None):
+        """mxec_encode_update_strided_device: parity_out = parity_in ^ the
+        parity of data shards [first, first + count) alone; data_ptr points at
+        shard `first`, parity_in_ptr None / 0 reads as zeros.  Enqueue-only."""
+        _check(self._lib.mxec_encode_update_strided_device(
+            self._h, dev, stream, k, m, shard_size, n_obj, first, count, data_ptr, data_obj_stride,
+            data_shard_stride, _u64p(data_len) if data_len is not None else None, parity_in_ptr or None,
+            in_obj_stride, in_shard_stride, parity_out_ptr, out_obj_stride, out_shard_stride))
+
     def encode_batch_device(self, objs: Sequence[tuple], data_ptrs, parity_ptrs, data_len=None,
                             digests_ptr=None, dev=0, stream=None):
         """Objects of mixed (k, m, shard_size); one launch per m."""
@@ -672,6 +684,10 @@ class Context:
     def open_reader(self, ec_dir: str, offset: int = 0, length: Optional[int] = None,
                     batch_bytes: int = 0) -> "ChunkReader":
         return ChunkReader(self, ec_dir, offset, length, batch_bytes)
+
+    def open_writer(self, ec_dir: str, chunk_size: int, parity_shards: int, total_len: int,
+                    plaintext_size: Optional[int] = None, window_bytes: int = 0) -> "ChunkWriter":
+        return ChunkWriter(self, ec_dir, chunk_size, parity_shards, total_len, plaintext_size, window_bytes)
 
     def body_sums(self, bodies: Sequence, which: int = 0x1F) -> list[dict]:
         """mxec_body_sums_batch: digests of host bodies (one dict each)."""
@@ -913,6 +929,53 @@ class ChunkReader:
 
     def __exit__(self, *exc):
         self.close()
+
+    def __del__(self):
+        self.close()
+
+
+class ChunkWriter:
+    """put_object_chunked (filesystem.rs:686-773) as a push stream over
+    mxec_writer_*: ``write(b)`` takes the body in pieces of any size,
+    ``finish()`` writes the parity files and manifest.json.  The body's length
+    is declared at open.  As a context manager it finishes on a clean exit and
+    only closes on an exception (no manifest is written then)."""
+
+    def __init__(self, ctx: "Context", ec_dir: str, chunk_size: int, parity_shards: int, total_len: int,
+                 plaintext_size: Optional[int] = None, window_bytes: int = 0):
+        self._lib = ctx._lib
+        self._ctx = ctx  # keeps the device context alive while the writer is open
+        self._w = None
+        self._finished = False
+        h = ctypes.c_void_p()
+        _check(self._lib.mxec_writer_open(ctx._h, ec_dir.encode() if ec_dir is not None else None, chunk_size,
+                                          parity_shards, total_len,
+                                          (1 << 64) - 1 if plaintext_size is None else plaintext_size,
+                                          window_bytes, ctypes.byref(h)))
+        self._w = h
+
+    def write(self, data) -> None:
+        b = _u8(data)
+        _check(self._lib.mxec_writer_write(self._w, _ptr(b) if b.size else None, b.size))
+
+    def finish(self) -> None:
+        _check(self._lib.mxec_writer_finish(self._w))
+        self._finished = True
+
+    def close(self) -> None:
+        if self._w:
+            self._lib.mxec_writer_close(self._w)
+            self._w = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *exc):
+        try:
+            if exc_type is None and not self._finished:
+                self.finish()
+        finally:
+            self.close()
 
     def __del__(self):
         self.close()

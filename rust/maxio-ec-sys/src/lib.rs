@@ -248,6 +248,7 @@ extern "C" {
     pub fn mxec_put_object_chunked_async(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, body: *const u8, len: usize, ticket: *mut *mut MxecTicket) -> c_int;
     pub fn mxec_get_object_chunked_async(ctx: *mut MxecCtx, ec_dir: *const c_char, offset: u64, length: u64, out: *mut u8, out_cap: u64, out_len: *mut u64, ticket: *mut *mut MxecTicket) -> c_int;
     pub fn mxec_encode_strided_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, k: c_int, m: c_int, shard_size: u64, n_obj: u64, data: *const u8, data_obj_stride: u64, data_shard_stride: u64, data_len: *const u64, parity: *mut u8, parity_obj_stride: u64, parity_shard_stride: u64, digests_dev: *mut u8) -> c_int;
+    pub fn mxec_encode_update_strided_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, k: c_int, m: c_int, shard_size: u64, n_obj: u64, first: c_int, count: c_int, data: *const u8, data_obj_stride: u64, data_shard_stride: u64, data_len: *const u64, parity_in: *const u8, in_obj_stride: u64, in_shard_stride: u64, parity_out: *mut u8, out_obj_stride: u64, out_shard_stride: u64) -> c_int;
     pub fn mxec_encode_batch_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, objs: *const MxecObject, n_obj: u64, data: *const *const u8, data_len: *const u64, parity: *const *mut u8, digests_dev: *mut u8) -> c_int;
     pub fn mxec_verify(ctx: *mut MxecCtx, k: c_int, m: c_int, shard_size: usize, data: *const *const u8, data_len: *const usize, parity: *const *const u8, first_bad: *mut u64, consistent: *mut c_int) -> c_int;
     pub fn mxec_verify_strided_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, k: c_int, m: c_int, shard_size: u64, n_obj: u64, data: *const u8, data_obj_stride: u64, data_shard_stride: u64, data_len: *const u64, parity: *const u8, parity_obj_stride: u64, parity_shard_stride: u64, first_bad_dev: *mut u64) -> c_int;
@@ -276,6 +277,10 @@ extern "C" {
     pub fn mxec_complete_multipart_chunked_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, parts: *const MxecMultipartPart, n_parts: u32, upload_key: *const u8, upload_id: *const c_char, key: *const u8, nonce_prefix: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, etag_out: *mut c_char) -> c_int;
     pub fn mxec_get_object_chunked(ctx: *mut MxecCtx, ec_dir: *const c_char, offset: u64, length: u64, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
     pub fn mxec_get_object_chunked_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, key: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, frame_size: u32, plaintext_size: u64, offset: u64, length: u64, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
+    pub fn mxec_writer_open(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, total_len: u64, plaintext_size: u64, window_bytes: u64, out: *mut *mut c_void) -> c_int;
+    pub fn mxec_writer_write(w: *mut c_void, buf: *const u8, len: u64) -> c_int;
+    pub fn mxec_writer_finish(w: *mut c_void) -> c_int;
+    pub fn mxec_writer_close(w: *mut c_void);
     pub fn mxec_reader_open(ctx: *mut MxecCtx, ec_dir: *const c_char, offset: u64, length: u64, batch_bytes: u64, out: *mut *mut MxecReader) -> c_int;
     pub fn mxec_reader_read(r: *mut MxecReader, buf: *mut u8, cap: u64) -> i64;
     pub fn mxec_reader_close(r: *mut MxecReader);
