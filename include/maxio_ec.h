@@ -645,6 +645,32 @@ int mxec_body_sums_batch(mxec_ctx* ctx, const uint8_t* const* bodies, const uint
 int mxec_body_sums_batch_device(mxec_ctx* ctx, int dev, void* stream,
                                 const uint8_t* const* bodies_dev, const uint64_t* lens,
                                 uint64_t n, uint32_t which, mxec_body_sums* out_dev);
+/* The same digests over bodies that arrive in pieces: replaces Md5::update /
+ * ChecksumHasher::update per stream piece (filesystem.rs:722-725) and their
+ * finalize (:775-777).  There are n bodies; body i's running state is the
+ * record at state_dev + i * MXEC_SUMS_STATE_BYTES, device memory of the
+ * caller's (16-byte aligned, layout private to the library) that need not be
+ * initialised before a FIRST call: FIRST starts every body from scratch,
+ * whatever its record holds.  Each call takes the next piece of every body
+ * (host array of device pointers, any length including 0, any alignment; a
+ * pointer may be NULL when its length is 0) and is enqueue-only on `stream`:
+ * no call waits for the GPU, so pieces may come and go through a bounded
+ * window.  Calls on one record must be stream-ordered and use the same
+ * `which`.  With FINAL, out_dev[i] receives exactly what
+ * mxec_body_sums_batch_device writes for the concatenation of body i's pieces
+ * since FIRST (fields not requested are left untouched); FIRST | FINAL in one
+ * call is that call.  out_dev is read only with FINAL and may be NULL
+ * otherwise.  MXEC_E_INVALID_ARG, decided before anything is enqueued: unknown
+ * `which` or `flags` bits, a null or misaligned state_dev, a null out_dev
+ * with FINAL, a null piece of non-zero length.  n == 0 or which == 0 is
+ * MXEC_OK and does nothing. */
+#define MXEC_SUMS_STATE_BYTES 512u
+#define MXEC_SUMS_F_FIRST 1u
+#define MXEC_SUMS_F_FINAL 2u
+int mxec_body_sums_update_device(mxec_ctx* ctx, int dev, void* stream,
+                                 const uint8_t* const* pieces_dev, const uint64_t* lens,
+                                 uint64_t n, uint32_t which, uint32_t flags,
+                                 void* state_dev, mxec_body_sums* out_dev);
 /* put_object_chunked plus the body digests it computes on the way
  * (PutResult etag / checksum_value, filesystem.rs:775-777). */
 int mxec_put_object_chunked_sums(mxec_ctx* ctx, const char* ec_dir,
@@ -741,13 +767,41 @@ int mxec_complete_multipart_chunked_encrypted(mxec_ctx* ctx, const char* ec_dir,
  * than a piece of a chunk on the host.
  * Threads: one writer is used by one thread at a time; any number of writers
  * run concurrently on a context, each on a stream of its own, sharing a slot
- * lock only within a call. */
+ * lock only within a call.
+ *
+ * mxec_writer_open_sums / mxec_writer_sums: the loop's Md5 and ChecksumHasher
+ * (filesystem.rs:700-725) and PutResult.etag / checksum_value (:775-777)
+ * inside the writer.  `which` (MXEC_SUM_*) names the body digests wanted;
+ * 0 is mxec_writer_open.  They advance on a stream of their own in runs over
+ * bytes already in the window (mxec_body_sums_update_device): a run ends at a
+ * chunk's end or at each whole MiB of a chunk and is queued as soon as its
+ * last byte's upload is, so however small the writes are there is one launch
+ * per run, and a body that arrives slower than the chains run pays at most
+ * one run's chain after its last byte.  A window slot is reused once its
+ * chunk's last run has finished too; write() still waits for the GPU only
+ * when the window is full.  finish() also brings the 76-byte record down (an
+ * empty body is one run of length 0).  mxec_writer_sums after a successful
+ * finish copies the requested fields into *out (the others are left
+ * untouched): what mxec_put_object_chunked_sums returns for the concatenated
+ * body.  Before a finish it is MXEC_E_INVALID_ARG ("sums before finish"); on
+ * a poisoned writer, the poisoning error; with which == 0, MXEC_OK and
+ * nothing written.
+ * The digests are of the bytes written: a caller who pushes an
+ * encrypt-then-EC frame stream (plaintext_size set) gets the frame stream's
+ * digests, not the plaintext's as mxec_put_object_chunked_encrypted returns.
+ * One lone fast body pays for them: its wall time becomes the slowest
+ * requested chain's (MD5: about 13 ns per byte against 1.1 on a CPU core);
+ * they pay with many bodies in flight. */
 typedef struct mxec_writer mxec_writer;
 int mxec_writer_open(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size,
                      uint32_t parity_shards, uint64_t total_len, uint64_t plaintext_size,
                      uint64_t window_bytes, void** out);
+int mxec_writer_open_sums(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size,
+                          uint32_t parity_shards, uint64_t total_len, uint64_t plaintext_size,
+                          uint64_t window_bytes, uint32_t which, void** out);
 int mxec_writer_write(void* w, const uint8_t* buf, uint64_t len);
 int mxec_writer_finish(void* w);
+int mxec_writer_sums(void* w, mxec_body_sums* out);
 void mxec_writer_close(void* w);
 
 /* GET of a whole EC object (VerifiedChunkReader over manifest.json,

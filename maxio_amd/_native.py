@@ -201,14 +201,18 @@ _SIGS = {
     "mxec_frames_decrypt_device": (INT, [P, INT, P, P, U64, ctypes.POINTER(ctypes.c_int32)]),
     "mxec_frame_aads": (INT, [P, P, ctypes.c_uint32, U64, U64, P]),
     "mxec_body_sums_batch_device": (INT, [P, INT, P, PP, U64P, U64, ctypes.c_uint32, P]),
+    "mxec_body_sums_update_device": (INT, [P, INT, P, PP, U64P, U64, ctypes.c_uint32, ctypes.c_uint32, P, P]),
     "mxec_get_object_chunked": (INT, [P, ctypes.c_char_p, U64, U64, P, U64, U64P]),
     "mxec_get_object_chunked_encrypted": (INT, [P, ctypes.c_char_p, P, P, ctypes.c_uint32, ctypes.c_uint32, U64,
                                                 U64, U64, P, U64, U64P]),
     "mxec_try_reconstruct_data_chunk": (INT, [P, ctypes.c_char_p, ctypes.c_uint32, P, U64, U64P]),
     "mxec_writer_open": (INT, [P, ctypes.c_char_p, U64, ctypes.c_uint32, U64, U64, U64,
                                ctypes.POINTER(ctypes.c_void_p)]),
+    "mxec_writer_open_sums": (INT, [P, ctypes.c_char_p, U64, ctypes.c_uint32, U64, U64, U64, ctypes.c_uint32,
+                                    ctypes.POINTER(ctypes.c_void_p)]),
     "mxec_writer_write": (INT, [P, P, U64]),
     "mxec_writer_finish": (INT, [P]),
+    "mxec_writer_sums": (INT, [P, P]),
     "mxec_writer_close": (None, [P]),
     "mxec_reader_open": (INT, [P, ctypes.c_char_p, U64, U64, U64, ctypes.POINTER(ctypes.c_void_p)]),
     "mxec_reader_read": (ctypes.c_int64, [P, P, U64]),

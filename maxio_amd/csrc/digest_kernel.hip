@@ -14,6 +14,7 @@
 //   and applies init / final xor.  See DESIGN.md §4 for the algebra.
 #include "hash_device.hpp"
 #include "kernels.hpp"
+#include "sums_carry.hpp"
 
 #include <cstdlib>
 
@@ -283,6 +284,97 @@ __global__ __launch_bounds__(64) void body_hash_kernel(BodyHashArgs a) {
     }
 }
 
+// ---- the update form: a chain that resumes --------------------------------------
+//
+// A body arrives in pieces; between two launches its chain lives in its
+// SumsChain (kernels.hpp): chaining words, byte count, and the bytes of the
+// block that is not full yet.  A piece first completes that block (bytewise,
+// through the record), then its full blocks go through hash_blocks exactly as
+// the one-shot kernel's do -- the register ring whenever what is left of the
+// piece starts 16-byte aligned, which is every piece of a stream cut at
+// multiples of 64 -- and what remains is kept for the next piece.  Nothing is
+// added inside the per-block loop; the arithmetic is sums_carry.hpp's.
+
+// The 16 words of a block kept in a record, as hash_blocks hands them on.
+__device__ __forceinline__ void load_tail_block(const uint32_t* t, u32x4 (&blk)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) blk[q] = u32x4{t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]};
+}
+
+// One lane's piece of one chain.  NW chaining words; LE: MD5's byte order.
+template <int NW, bool LE, class Compress>
+__device__ __forceinline__ void chain_update(const BodyHashUpdArgs& a, uint32_t i, SumsChain& c,
+                                             const uint32_t (&iv)[NW], uint32_t out_off, Compress compress) {
+    const uint8_t* p = a.h.ptrs[i];
+    const uint64_t len = a.h.lens[i];
+    uint32_t st[NW];
+    uint64_t bytes = 0;
+    if (a.flags & kSumsFirst) {
+#pragma unroll
+        for (int t = 0; t < NW; ++t) st[t] = iv[t];
+    } else {
+#pragma unroll
+        for (int t = 0; t < NW; ++t) st[t] = c.h[t];
+        bytes = c.bytes;
+    }
+    const SumsCarry k = sums_carry(uint32_t(bytes) & 63u, len);
+    uint8_t* tail = reinterpret_cast<uint8_t*>(c.tail);
+    auto words = [](const u32x4(&blk)[4], uint32_t(&x)[16]) {
+        if constexpr (LE) words_le(blk, x);
+        else block_words(blk, x);
+    };
+    auto comp = [&](uint32_t(&x)[16]) { compress(st, x); };
+    uint32_t w[16];
+    if (k.take) {
+        for (uint32_t t = 0; t < k.take; ++t) tail[k.head - k.take + t] = p[t];
+        if (k.head == 64) {
+            u32x4 blk[4];
+            load_tail_block(c.tail, blk);
+            words(blk, w);
+            comp(w);
+        }
+    }
+    const uint8_t* q = p + k.take;
+    hash_blocks(q, k.blocks, comp, words);
+    q += 64 * k.blocks;
+    for (uint32_t t = 0; t < k.rest; ++t) tail[t] = q[t];  // head is 0 or 64 whenever rest > 0
+#pragma unroll
+    for (int t = 0; t < NW; ++t) c.h[t] = st[t];
+    c.bytes = bytes + len;
+    if (!(a.flags & kSumsFinal)) return;
+    const int nblk = sums_pad_blocks(k.tail);
+    const uint64_t bits = (bytes + len) * 8;
+    for (int blk = 0; blk < nblk; ++blk) {
+#pragma unroll
+        for (int t = 0; t < 16; ++t)
+            w[t] = LE ? tail_word_le(tail, k.tail, 16 * blk + t, nblk, bits) : tail_word(tail, k.tail, 16 * blk + t, nblk, bits);
+        comp(w);
+    }
+    uint32_t* o = reinterpret_cast<uint32_t*>(a.h.out + uint64_t(i) * a.h.out_stride + out_off);
+#pragma unroll
+    for (int t = 0; t < NW; ++t) o[t] = LE ? st[t] : bswap(st[t]);
+}
+
+// The same shape as body_hash_kernel: one lane per body, blockIdx.y picks the
+// algorithm and with it the chain of the record this block owns.
+__global__ __launch_bounds__(64) void body_hash_update_kernel(BodyHashUpdArgs a) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= a.h.n) return;
+    const uint32_t alg = a.h.algs[blockIdx.y];
+    SumsChain& c = reinterpret_cast<SumsState*>(a.state + uint64_t(i) * a.state_stride)->chain[alg];
+    if (alg == kBodyMd5) {
+        const uint32_t iv[4] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u};
+        chain_update<4, true>(a, i, c, iv, a.h.off_md5, [](uint32_t(&st)[4], uint32_t(&x)[16]) { md5_compress(st, x); });
+    } else if (alg == kBodySha1) {
+        const uint32_t iv[5] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u, 0xc3d2e1f0u};
+        chain_update<5, false>(a, i, c, iv, a.h.off_sha1, [](uint32_t(&st)[5], uint32_t(&x)[16]) { sha1_compress(st, x); });
+    } else {
+        const uint32_t iv[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                                0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+        chain_update<8, false>(a, i, c, iv, a.h.off_sha256, [](uint32_t(&st)[8], uint32_t(&x)[16]) { compress(st, x); });
+    }
+}
+
 // ---- CRC32 / CRC32C ------------------------------------------------------------
 //
 // Raw CRC R(M) (register starts at 0, no final xor) is linear:
@@ -432,14 +524,11 @@ __global__ __launch_bounds__(256) void crc_tiles_kernel(CrcArgs a) {
     }
 }
 
-// One workgroup per body: fold its tiles, the tail bytes, init and xorout.
-__global__ __launch_bounds__(256) void crc_finish_kernel(CrcArgs a) {
-    __shared__ uint32_t red[4];
-    const uint32_t body = blockIdx.x;
-    if (body >= a.n_bodies) return;
+// One workgroup per body: its tiles and tail bytes folded to the raw CRC of
+// the body (or piece), which lane 0 gets (true); the other lanes get false.
+__device__ __forceinline__ bool crc_body_raw(const CrcArgs& a, const CrcBody& bd, uint32_t* red, uint32_t* out) {
     const CrcTables* tb = a.tables;
     const uint32_t poly = tb->poly;
-    const CrcBody bd = a.bodies[body];
     const uint32_t lane = threadIdx.x;
     // Lane l folds tiles [l*q, min((l+1)*q, n)) then shifts by the tiles after.
     const uint64_t n = bd.n_tiles;
@@ -458,18 +547,52 @@ __global__ __launch_bounds__(256) void crc_finish_kernel(CrcArgs a) {
     for (int s = 32; s >= 1; s >>= 1) acc ^= __shfl_xor(acc, s);
     if ((lane & 63) == 0) red[lane >> 6] = acc;
     __syncthreads();
-    if (lane != 0) return;
+    if (lane != 0) return false;
     uint32_t raw = red[0] ^ red[1] ^ red[2] ^ red[3];
     // Tail bytes [tail, tail + tail_len), byte at a time (< 16 of them).
     for (uint32_t t = 0; t < bd.tail_len; ++t) {
         const uint32_t b = bd.tail[t];
         raw = (raw >> 8) ^ tb->slice[15][(raw ^ b) & 0xFF];
     }
-    // C = R ^ shift(~v, len) ^ 0xFFFFFFFF
-    uint32_t init = ~bd.prev;
-    for (uint64_t e = bd.len, j = 0; e; ++j, e >>= 1)
-        if (e & 1) init = multmodp(tb->byte_pow[j], init, poly);
-    *reinterpret_cast<uint32_t*>(a.out + uint64_t(body) * a.out_stride) = raw ^ init ^ 0xFFFFFFFFu;
+    *out = raw;
+    return true;
+}
+
+// C = R ^ shift(~v, len) ^ 0xFFFFFFFF: the standard CRC of a message of raw
+// CRC R and length len behind the running value v.
+__device__ __forceinline__ uint32_t crc_continue(const CrcTables* tb, uint32_t v, uint32_t raw, uint64_t len) {
+    uint32_t init = ~v;
+    for (uint64_t e = len, j = 0; e; ++j, e >>= 1)
+        if (e & 1) init = multmodp(tb->byte_pow[j], init, tb->poly);
+    return raw ^ init ^ 0xFFFFFFFFu;
+}
+
+// Fold a body's tiles and tail bytes, apply init / final xor.
+__global__ __launch_bounds__(256) void crc_finish_kernel(CrcArgs a) {
+    __shared__ uint32_t red[4];
+    const uint32_t body = blockIdx.x;
+    if (body >= a.n_bodies) return;
+    const CrcBody bd = a.bodies[body];
+    uint32_t raw;
+    if (!crc_body_raw(a, bd, red, &raw)) return;
+    *reinterpret_cast<uint32_t*>(a.out + uint64_t(body) * a.out_stride) = crc_continue(a.tables, bd.prev, raw, bd.len);
+}
+
+// The update form: the value to continue is the body's record's, where the
+// new one goes back; with kSumsFinal it is the body's CRC.
+__global__ __launch_bounds__(256) void crc_finish_update_kernel(CrcArgs a, CrcCarry c) {
+    __shared__ uint32_t red[4];
+    const uint32_t body = blockIdx.x;
+    if (body >= a.n_bodies) return;
+    const CrcBody bd = a.bodies[body];
+    uint32_t raw;
+    if (!crc_body_raw(a, bd, red, &raw)) return;
+    SumsCrc& run = reinterpret_cast<SumsState*>(c.state + uint64_t(body) * c.state_stride)->crc[c.poly];
+    const bool first = c.flags & kSumsFirst;
+    const uint32_t v = crc_continue(a.tables, first ? 0u : run.value, raw, bd.len);
+    run.bytes = (first ? 0 : run.bytes) + bd.len;
+    run.value = v;
+    if (c.flags & kSumsFinal) *reinterpret_cast<uint32_t*>(a.out + uint64_t(body) * a.out_stride) = v;
 }
 
 }  // namespace
@@ -480,29 +603,52 @@ hipError_t launch_body_hash(const BodyHashArgs& a, uint32_t n_algs, hipStream_t 
     return hipGetLastError();
 }
 
+hipError_t launch_body_hash_update(const BodyHashUpdArgs& a, uint32_t n_algs, hipStream_t s) {
+    if (a.h.n == 0 || n_algs == 0) return hipSuccess;
+    hipLaunchKernelGGL(body_hash_update_kernel, dim3((a.h.n + 63) / 64, n_algs), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
 uint64_t crc_tile_bytes() { return uint64_t(kCrcRows) * 256 * 16; }
+
+namespace {
+// The tile pass (a.n_tiles > 0).
+hipError_t launch_crc_tiles(const CrcArgs& a, int n_cus, hipStream_t s) {
+    // 128 workgroups per CU of grid-stride: 8 / 32 / 128 / 512 measured
+    // 4.70 / 4.74 / 4.81 / 4.79 TB/s (profiles/r2_crc_grid_ab.txt; more,
+    // shorter workgroups keep the tiles in flight together, as for RS).
+#ifdef MXEC_LAB
+    static const uint64_t bpc = [] {  // MXEC_CRC_BPC: lab override
+        const char* e = getenv("MXEC_CRC_BPC");
+        const long v = e ? atol(e) : 0;
+        return v > 0 && v <= 4096 ? uint64_t(v) : uint64_t(128);
+    }();
+#else
+    constexpr uint64_t bpc = 128;
+#endif
+    const uint64_t grid = std::min<uint64_t>(a.n_tiles, uint64_t(n_cus) * bpc);
+    hipLaunchKernelGGL(crc_tiles_kernel, dim3(uint32_t(grid)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+}  // namespace
 
 hipError_t launch_crc(const CrcArgs& a, int n_cus, hipStream_t s) {
     if (a.n_bodies == 0) return hipSuccess;
     if (a.n_tiles) {
-        // 128 workgroups per CU of grid-stride: 8 / 32 / 128 / 512 measured
-        // 4.70 / 4.74 / 4.81 / 4.79 TB/s (profiles/r2_crc_grid_ab.txt; more,
-        // shorter workgroups keep the tiles in flight together, as for RS).
-#ifdef MXEC_LAB
-        static const uint64_t bpc = [] {  // MXEC_CRC_BPC: lab override
-            const char* e = getenv("MXEC_CRC_BPC");
-            const long v = e ? atol(e) : 0;
-            return v > 0 && v <= 4096 ? uint64_t(v) : uint64_t(128);
-        }();
-#else
-        constexpr uint64_t bpc = 128;
-#endif
-        const uint64_t grid = std::min<uint64_t>(a.n_tiles, uint64_t(n_cus) * bpc);
-        hipLaunchKernelGGL(crc_tiles_kernel, dim3(uint32_t(grid)), dim3(256), 0, s, a);
-        hipError_t e = hipGetLastError();
+        hipError_t e = launch_crc_tiles(a, n_cus, s);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(crc_finish_kernel, dim3(a.n_bodies), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_crc_update(const CrcArgs& a, const CrcCarry& c, int n_cus, hipStream_t s) {
+    if (a.n_bodies == 0) return hipSuccess;
+    if (a.n_tiles) {
+        hipError_t e = launch_crc_tiles(a, n_cus, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(crc_finish_update_kernel, dim3(a.n_bodies), dim3(256), 0, s, a, c);
     return hipGetLastError();
 }
 

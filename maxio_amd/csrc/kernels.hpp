@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "../../include/maxio_ec.h"
 #include "rs_args.hpp"
 
 namespace mxec {
@@ -115,6 +116,38 @@ struct BodyHashArgs {
 };
 hipError_t launch_body_hash(const BodyHashArgs& a, uint32_t n_algs, hipStream_t s);
 
+// A body's digests between two pieces (mxec_body_sums_update_device): one
+// record of MXEC_SUMS_STATE_BYTES per body in the caller's HBM.  Every
+// launch row owns its part: a chain per algorithm, each with its own tail (the
+// three run side by side in one launch), and a running value per polynomial.
+struct alignas(16) SumsChain {
+    uint32_t h[8];      // chaining words (MD5 4, SHA-1 5, SHA-256 8)
+    uint64_t bytes;     // hashed or pending so far; bytes % 64 are pending in tail
+    uint64_t _pad;
+    uint32_t tail[16];  // the unfinished block's bytes, in message order
+};
+struct SumsCrc {
+    uint64_t bytes;  // covered by value
+    uint32_t value;  // as crc32fast / crc32c_append hold it after those bytes
+    uint32_t _pad;
+};
+struct alignas(16) SumsState {
+    SumsChain chain[3];  // by kBody*
+    SumsCrc crc[2];      // CRC32, CRC32C
+};
+static_assert(sizeof(SumsState) <= MXEC_SUMS_STATE_BYTES, "SumsState outgrew the caller's record");
+constexpr uint32_t kSumsFirst = MXEC_SUMS_F_FIRST, kSumsFinal = MXEC_SUMS_F_FINAL;
+// The update form: body i's piece continues state[i] (from the IV with
+// kSumsFirst) and leaves its state there; with kSumsFinal it is padded with
+// the total length and the digest goes to `out` as launch_body_hash writes it.
+struct BodyHashUpdArgs {
+    BodyHashArgs h;    // ptrs / lens: the pieces (a pointer may be null when its length is 0)
+    uint8_t* state;    // [n] records of state_stride bytes (SumsState)
+    uint64_t state_stride;
+    uint32_t flags;    // kSums*
+};
+hipError_t launch_body_hash_update(const BodyHashUpdArgs& a, uint32_t n_algs, hipStream_t s);
+
 // Per-polynomial constants (reflected domain), built on the host.
 struct CrcTables {
     uint32_t poly;
@@ -149,6 +182,18 @@ struct CrcArgs {
 };
 uint64_t crc_tile_bytes();
 hipError_t launch_crc(const CrcArgs& a, int n_cus, hipStream_t s);
+// The update form of the finisher: the value to continue comes from
+// state[body].crc[poly] instead of CrcBody::prev (0 with kSumsFirst) and the
+// new running value goes back there; with kSumsFinal it also goes to a.out.
+// The tile pass is launch_crc's: a piece's raw CRC does not depend on what
+// came before it.
+struct CrcCarry {
+    uint8_t* state;  // [n_bodies] records of state_stride bytes (SumsState)
+    uint64_t state_stride;
+    uint32_t poly;   // 0 CRC32, 1 CRC32C
+    uint32_t flags;  // kSums*
+};
+hipError_t launch_crc_update(const CrcArgs& a, const CrcCarry& c, int n_cus, hipStream_t s);
 
 // ---- encrypt-then-EC frames (gcm_kernel.hip) ----------------------------------
 // Per object (data key): AES-256 round keys as big-endian words, H^1..H^256

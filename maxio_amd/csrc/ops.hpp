@@ -175,8 +175,18 @@ inline bool copy_waves_put(const Device& d) { return d.kn && d.kn->pipe_copy == 
 
 // PUT body digests of device-resident bodies into mxec_body_sums records
 // (sums.cpp); enqueued on s.
+// upd: the update form (mxec_body_sums_update_device) -- ptrs / lens are the
+// next piece of every body, whose state is the record at state_dev +
+// i * MXEC_SUMS_STATE_BYTES; out_dev is written with MXEC_SUMS_F_FINAL only.
+// arena: the tables from it instead of the slot's ring, whose entries a
+// caller with many runs queued behind a slow chain would wait for.
+struct SumsUpdate {
+    uint8_t* state_dev;
+    uint32_t flags;  // MXEC_SUMS_F_*
+};
 int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const uint8_t*>& ptrs,
-                  const std::vector<uint64_t>& lens, uint32_t which, uint8_t* out_dev, uint64_t stride);
+                  const std::vector<uint64_t>& lens, uint32_t which, uint8_t* out_dev, uint64_t stride,
+                  const SumsUpdate* upd = nullptr, DescArena* arena = nullptr);
 
 // Creates the device's host-pipeline hub and its streams (pipe_hub.cpp),
 // called by mxec_open for every device.

@@ -15,6 +15,13 @@
 // fold): side by side they take one chain's time, not two.  A slot is reused
 // once its chunk's hash and parity pass have finished -- the only device wait
 // inside write().
+//
+// Body digests (mxec_writer_open_sums): the Md5 and ChecksumHasher of the
+// reference's loop (filesystem.rs:700-725) advance on one more stream, in
+// runs of at most 1 MiB over bytes already in the window, each queued behind
+// its last byte's upload (run_body_sums' update form; the chains' state stays
+// in HBM between runs, so nothing waits between them).  A slot's reuse then
+// also waits for its chunk's last run.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -38,7 +45,15 @@ struct WindowSlot {
     hipEvent_t folded = nullptr;    // the chunk's parity pass on the main stream finished
     uint64_t chunk = UINT64_MAX;    // the chunk whose digest has not been collected yet
     uint64_t dig_at = 0;            // ... and its entry in the digest landing zone
+    // With body digests: the chunk's last run on the digest stream finished,
+    // and the launch tables of its runs (free again once it has).
+    hipEvent_t summed = nullptr;
+    DescArena sum_tables;
 };
+
+// Table bytes one digest run takes (pointers, CRC tile map and scratch of at
+// most kSumRun bytes; the arena chains a block should one take more).
+constexpr size_t kSumRunTables = 512;
 
 }  // namespace
 
@@ -70,6 +85,15 @@ struct mxec_writer {
     std::vector<std::string> sha;  // the manifest's entries: k data digests, then m parity
     int fd = -1;                   // the open chunk file
 
+    // Body digests (mxec_writer_open_sums; which == 0: none of this exists).
+    uint32_t which = 0;
+    hipStream_t sum_s = nullptr;    // the digest runs, in body order
+    hipEvent_t sums_done = nullptr;  // the last run and the record's way down
+    DevBuf sum_state;               // the body's state record, then its mxec_body_sums
+    PinnedBuf hsums;                // ... landed
+    mxec_body_sums sums{};          // after finish()
+    uint8_t* sums_out_dev() const { return static_cast<uint8_t*>(sum_state.p) + MXEC_SUMS_STATE_BYTES; }
+
     uint8_t* slot_ptr(uint64_t slot) const { return static_cast<uint8_t*>(window.p) + slot * sa; }
     uint8_t* parity_set(int which) const { return static_cast<uint8_t*>(parity.p) + uint64_t(which) * m * sa; }
 
@@ -79,7 +103,14 @@ struct mxec_writer {
         (void)hipSetDevice(dev->id);
         // Nothing of ours may still run when the buffers go.
         if (s) (void)hipStreamSynchronize(s);
+        if (sum_s) {
+            (void)hipStreamSynchronize(sum_s);
+            affinity_untag(sum_s);
+            (void)hipStreamDestroy(sum_s);
+        }
+        if (sums_done) (void)hipEventDestroy(sums_done);
         for (WindowSlot& w : slots) {
+            if (w.summed) (void)hipEventDestroy(w.summed);
             if (w.hash) {
                 (void)hipStreamSynchronize(w.hash);
                 affinity_untag(w.hash);
@@ -127,6 +158,7 @@ int collect(mxec_writer& w, uint64_t slot) {
     if (ws.chunk == UINT64_MAX) return MXEC_OK;
     MXEC_HIP(hipEventSynchronize(ws.hashed));
     if (w.m) MXEC_HIP(hipEventSynchronize(ws.folded));
+    if (w.which) MXEC_HIP(hipEventSynchronize(ws.summed));  // queued before the chunk completed
     w.sha[ws.chunk] = hex(static_cast<const uint8_t*>(w.hdig.p) + ws.dig_at * 32, 32);
     ws.chunk = UINT64_MAX;
     return MXEC_OK;
@@ -207,6 +239,29 @@ int close_chunk_file(mxec_writer& w, uint64_t j) {
     return MXEC_OK;
 }
 
+// One run of the body digests over bytes whose uploads are queued on w.s:
+// the next piece of the body's chains, on the digest stream behind them.
+int queue_sum_run(mxec_writer& w, const SumRun& r) {
+    const uint64_t slot = w.plan.slot_of(r.chunk);
+    WindowSlot& ws = w.slots[slot];
+    if (r.at == 0) MXEC_TRY(ws.sum_tables.reserve(size_t(writer_sum_runs_of(w.plan, r.chunk)) * kSumRunTables));
+    MXEC_HIP(hipEventRecord(w.uploaded, w.s));
+    MXEC_HIP(hipStreamWaitEvent(w.sum_s, w.uploaded, 0));
+    {
+        DevScope ds;
+        MXEC_TRY(ds.open(w.ctx, w.dev_index));
+        const SumsUpdate upd{static_cast<uint8_t*>(w.sum_state.p),
+                             (r.first ? MXEC_SUMS_F_FIRST : 0u) | (r.last ? MXEC_SUMS_F_FINAL : 0u)};
+        MXEC_TRY(run_body_sums(*ds.d, *ds.slot, w.sum_s, {w.slot_ptr(slot) + r.at}, {r.len}, w.which, w.sums_out_dev(),
+                               sizeof(mxec_body_sums), &upd, &ws.sum_tables));
+    }
+    if (r.closes) MXEC_HIP(hipEventRecord(ws.summed, w.sum_s));
+    if (!r.last) return MXEC_OK;
+    MXEC_HIP(hipMemcpyAsync(w.hsums.p, w.sums_out_dev(), sizeof(mxec_body_sums), hipMemcpyDeviceToHost, w.sum_s));
+    MXEC_HIP(hipEventRecord(w.sums_done, w.sum_s));
+    return MXEC_OK;
+}
+
 int take_run(mxec_writer& w, const WriterRun& r, const uint8_t* buf) {
     const uint64_t slot = w.plan.slot_of(r.chunk);
     if (r.opens) {
@@ -215,6 +270,8 @@ int take_run(mxec_writer& w, const WriterRun& r, const uint8_t* buf) {
     }
     MXEC_TRY(write_chunk_bytes(w, r.chunk, buf + r.src, r.len));
     MXEC_TRY(upload(w, w.slot_ptr(slot) + r.at, buf + r.src, r.len));
+    if (w.which)
+        MXEC_TRY(writer_sum_due(w.plan, r.chunk, r.at, r.at + r.len, [&](const SumRun& q) { return queue_sum_run(w, q); }));
     if (!r.completes) return MXEC_OK;
     MXEC_TRY(close_chunk_file(w, r.chunk));
     return complete(w, r.chunk);
@@ -249,6 +306,8 @@ int finish(mxec_writer& w) {
     if (w.plan.total_len == 0) {  // one empty chunk (:740-743), no parity (:748)
         MXEC_TRY(open_chunk_file(w, 0));
         MXEC_TRY(close_chunk_file(w, 0));
+        if (w.which)  // one empty run, first and last
+            MXEC_TRY(writer_sum_due(w.plan, 0, 0, 0, [&](const SumRun& q) { return queue_sum_run(w, q); }));
         MXEC_TRY(complete(w, 0));
     }
     const uint64_t k = w.plan.k;
@@ -257,6 +316,10 @@ int finish(mxec_writer& w) {
     for (uint64_t slot = 0; slot < w.slots.size(); ++slot) MXEC_TRY(collect(w, slot));
     const uint8_t* hd = static_cast<const uint8_t*>(w.hdig.p) + (w.slots.size() + 1) * 32;  // landed with the last chunk's
     for (uint32_t i = 0; i < w.m; ++i) w.sha[k + i] = hex(hd + size_t(i) * 32, 32);
+    if (w.which) {  // queued with the body's last byte
+        MXEC_HIP(hipEventSynchronize(w.sums_done));
+        std::memcpy(&w.sums, w.hsums.p, sizeof w.sums);
+    }
     Manifest man;
     man.version = w.m ? 2 : 1;
     man.total_size = w.plan.total_len;
@@ -274,16 +337,13 @@ int finish(mxec_writer& w) {
     return write_file(w.dir / "manifest.json", reinterpret_cast<const uint8_t*>(js.data()), js.size());
 }
 
-}  // namespace
-
-extern "C" {
-
-int mxec_writer_open(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uint32_t parity_shards,
-                     uint64_t total_len, uint64_t plaintext_size, uint64_t window_bytes, void** out) {
+int open_writer(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uint32_t parity_shards, uint64_t total_len,
+                uint64_t plaintext_size, uint64_t window_bytes, uint32_t which, void** out) {
     return guarded([&]() -> int {
         if (!ctx || !ec_dir || !out) return set_error(MXEC_E_INVALID_ARG, "null argument");
         *out = nullptr;
         if (chunk_size == 0) return set_error(MXEC_E_INVALID_ARG, "chunk_size must be > 0");
+        if (which & ~uint32_t(0x1F)) return set_error(MXEC_E_INVALID_ARG, "unknown digest flag");
         auto w = std::make_unique<mxec_writer>();
         w->plan = WriterPlan::make(chunk_size, total_len, window_bytes);
         w->m = parity_shards > 0 && total_len > 0 ? parity_shards : 0;  // :748
@@ -321,6 +381,18 @@ int mxec_writer_open(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uin
             MXEC_TRY(new_event(&ws.hashed));
             MXEC_TRY(new_event(&ws.folded));
         }
+        w->which = which;
+        if (which) {
+            MXEC_TRY(w->sum_state.ensure(MXEC_SUMS_STATE_BYTES + sizeof(mxec_body_sums)));
+            MXEC_TRY(w->hsums.ensure(sizeof(mxec_body_sums)));
+            MXEC_TRY(new_stream(*w, &w->sum_s));
+            MXEC_TRY(new_event(&w->sums_done));
+            for (WindowSlot& ws : w->slots) {
+                MXEC_TRY(new_event(&ws.summed));
+                ws.sum_tables.owner = d;
+                MXEC_TRY(ws.sum_tables.reserve(std::max<size_t>(4096, size_t(writer_sum_runs_of(w->plan, 0)) * kSumRunTables)));
+            }
+        }
         w->sha.resize(size_t(w->plan.k + w->m));
         std::error_code ec;
         fs::create_directories(w->dir, ec);
@@ -328,6 +400,21 @@ int mxec_writer_open(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uin
         *out = w.release();
         return MXEC_OK;
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int mxec_writer_open(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uint32_t parity_shards,
+                     uint64_t total_len, uint64_t plaintext_size, uint64_t window_bytes, void** out) {
+    return open_writer(ctx, ec_dir, chunk_size, parity_shards, total_len, plaintext_size, window_bytes, 0, out);
+}
+
+int mxec_writer_open_sums(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uint32_t parity_shards,
+                          uint64_t total_len, uint64_t plaintext_size, uint64_t window_bytes, uint32_t which,
+                          void** out) {
+    return open_writer(ctx, ec_dir, chunk_size, parity_shards, total_len, plaintext_size, window_bytes, which, out);
 }
 
 int mxec_writer_write(void* wp, const uint8_t* buf, uint64_t len) {
@@ -358,6 +445,24 @@ int mxec_writer_finish(void* wp) {
         const int rc = poison(*w, finish(*w));
         w->finished = rc == MXEC_OK;
         return rc;
+    });
+}
+
+int mxec_writer_sums(void* wp, mxec_body_sums* out) {
+    return guarded([&]() -> int {
+        auto* w = static_cast<mxec_writer*>(wp);
+        if (!w) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        if (w->err) return set_error(w->err, w->err_msg);
+        if (w->which == 0) return MXEC_OK;
+        if (!out) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        if (!w->finished) return set_error(MXEC_E_INVALID_ARG, "sums before finish");
+        const mxec_body_sums& h = w->sums;
+        if (w->which & MXEC_SUM_MD5) std::memcpy(out->md5, h.md5, 16);
+        if (w->which & MXEC_SUM_CRC32) out->crc32 = h.crc32;
+        if (w->which & MXEC_SUM_CRC32C) out->crc32c = h.crc32c;
+        if (w->which & MXEC_SUM_SHA1) std::memcpy(out->sha1, h.sha1, 20);
+        if (w->which & MXEC_SUM_SHA256) std::memcpy(out->sha256, h.sha256, 32);
+        return MXEC_OK;
     });
 }
 

@@ -1,4 +1,5 @@
-// sums.cpp — PUT body digests (include/maxio_ec.h mxec_body_sums_batch*).
+// sums.cpp — PUT body digests (include/maxio_ec.h mxec_body_sums_batch*,
+// mxec_body_sums_update_device).
 //
 // filesystem.rs:700-725 hashes every body byte with Md5 (the ETag, :775) and
 // the optional ChecksumHasher (:28-63).  MD5 / SHA-1 / SHA-256 run one lane per
@@ -110,7 +111,8 @@ namespace mxec {
 // Body digests of n device-resident bodies into records of `stride` bytes
 // (mxec_body_sums layout) at out_dev; everything is enqueued on `s`.
 int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const uint8_t*>& ptrs,
-                  const std::vector<uint64_t>& lens, uint32_t which, uint8_t* out_dev, uint64_t stride) {
+                  const std::vector<uint64_t>& lens, uint32_t which, uint8_t* out_dev, uint64_t stride,
+                  const SumsUpdate* upd, DescArena* arena) {
     const size_t n = ptrs.size();
     if (n == 0 || which == 0) return MXEC_OK;
     if (n > 0xFFFFFFFFull) return set_error(MXEC_E_INVALID_ARG, "too many bodies");
@@ -122,7 +124,7 @@ int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const 
     if (which & MXEC_SUM_CRC32) polys.push_back(0);
     if (which & MXEC_SUM_CRC32C) polys.push_back(1);
 
-    DescWriter w(slot);
+    DescWriter w(slot, arena);
     const size_t o_ptr = w.add(n * sizeof(void*));
     const size_t o_len = w.add(n * sizeof(uint64_t));
     const size_t o_alg = w.add(std::max<size_t>(1, algs.size()) * sizeof(uint32_t));
@@ -149,7 +151,7 @@ int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const 
         for (size_t i = 0; i < n; ++i)
             for (uint64_t t = 0; t < bodies[i].n_tiles; ++t) tb[bodies[i].tile0 + t] = uint32_t(i);
     }
-    MXEC_TRY(affinity_check(d, &slot, s, "run_body_sums"));
+    MXEC_TRY(affinity_check(d, &slot, s, "run_body_sums", arena));
     char* dev = nullptr;
     MXEC_TRY(w.commit(s, &dev));
     if (!polys.empty()) {
@@ -165,7 +167,12 @@ int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const 
             a.out_stride = stride;
             a.n_tiles = tiles;
             a.n_bodies = uint32_t(n);
-            MXEC_HIP(launch_crc(a, d.n_cus, s));
+            if (upd) {
+                const CrcCarry c{upd->state_dev, MXEC_SUMS_STATE_BYTES, uint32_t(polys[q]), upd->flags};
+                MXEC_HIP(launch_crc_update(a, c, d.n_cus, s));
+            } else {
+                MXEC_HIP(launch_crc(a, d.n_cus, s));
+            }
         }
     }
     if (!algs.empty()) {
@@ -179,7 +186,12 @@ int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const 
         h.off_sha1 = offsetof(mxec_body_sums, sha1);
         h.off_sha256 = offsetof(mxec_body_sums, sha256);
         h.n = uint32_t(n);
-        MXEC_HIP(launch_body_hash(h, uint32_t(algs.size()), s));
+        if (upd) {
+            const BodyHashUpdArgs u{h, upd->state_dev, MXEC_SUMS_STATE_BYTES, upd->flags};
+            MXEC_HIP(launch_body_hash_update(u, uint32_t(algs.size()), s));
+        } else {
+            MXEC_HIP(launch_body_hash(h, uint32_t(algs.size()), s));
+        }
     }
     return w.finish(s);
 }
@@ -202,6 +214,29 @@ int mxec_body_sums_batch_device(mxec_ctx* ctx, int dev, void* stream, const uint
         std::vector<uint64_t> l(lens, lens + n);
         return run_body_sums(*ds.d, *ds.slot, static_cast<hipStream_t>(stream), p, l, which,
                              reinterpret_cast<uint8_t*>(out_dev), sizeof(mxec_body_sums));
+    });
+}
+
+int mxec_body_sums_update_device(mxec_ctx* ctx, int dev, void* stream, const uint8_t* const* pieces_dev,
+                                 const uint64_t* lens, uint64_t n, uint32_t which, uint32_t flags, void* state_dev,
+                                 mxec_body_sums* out_dev) {
+    return guarded([&] {
+        if (which & ~uint32_t(0x1F)) return set_error(MXEC_E_INVALID_ARG, "unknown digest flag");
+        if (flags & ~(kSumsFirst | kSumsFinal)) return set_error(MXEC_E_INVALID_ARG, "unknown update flag");
+        if (n == 0 || which == 0) return MXEC_OK;
+        if (!pieces_dev || !lens) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        if (!state_dev) return set_error(MXEC_E_INVALID_ARG, "null state_dev");
+        if (reinterpret_cast<uintptr_t>(state_dev) & 15) return set_error(MXEC_E_INVALID_ARG, "state_dev is not 16-byte aligned");
+        if ((flags & kSumsFinal) && !out_dev) return set_error(MXEC_E_INVALID_ARG, "null out_dev with the final piece");
+        for (uint64_t i = 0; i < n; ++i)
+            if (lens[i] && !pieces_dev[i]) return set_error(MXEC_E_INVALID_ARG, "null piece pointer " + std::to_string(i));
+        DevScope ds;
+        MXEC_TRY(ds.open(ctx, dev));
+        std::vector<const uint8_t*> p(pieces_dev, pieces_dev + n);
+        std::vector<uint64_t> l(lens, lens + n);
+        const SumsUpdate upd{static_cast<uint8_t*>(state_dev), flags};
+        return run_body_sums(*ds.d, *ds.slot, static_cast<hipStream_t>(stream), p, l, which,
+                             reinterpret_cast<uint8_t*>(out_dev), sizeof(mxec_body_sums), &upd);
     });
 }
 

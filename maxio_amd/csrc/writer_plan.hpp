@@ -2,11 +2,12 @@
 // put_object_chunked filesystem.rs:686-773 as a push stream): how a declared
 // length becomes chunks, how one write() is cut into per-chunk runs, which
 // window slot a chunk takes and whose work it must wait for, and the over-run
-// and short-finish errors.  Only integers; nothing is read or written.
+// and short-finish errors, and which runs of the body digests are due as a
+// chunk's bytes arrive.  Only integers; nothing is read or written.
 //
 // Host-only (no HIP, no I/O): storage_writer.cpp calls it, and
-// tests/c_manifest/writer_plan_check.cpp runs it on its own under
-// -fsanitize=address,undefined.
+// tests/c_manifest/writer_plan_check.cpp and writer_sums_check.cpp run it on
+// their own under -fsanitize=address,undefined.
 #pragma once
 
 #include <cstdint>
@@ -85,6 +86,53 @@ int writer_cut(const WriterPlan& p, uint64_t written, uint64_t len, F&& f) {
         written += r.len;
     }
     return 0;
+}
+
+// The body digests of a writer opened with them advance in runs over bytes
+// already in the window: a run ends at its chunk's end or at each whole
+// kSumRun of the chunk, whichever comes first, so every chunk is tiled exactly
+// once and a run never crosses a slot.  The body's first run starts its
+// chains, its last one ends them.  An empty body's one empty chunk is one
+// empty run, first and last.
+constexpr uint64_t kSumRun = uint64_t(1) << 20;
+struct SumRun {
+    uint64_t chunk;
+    uint64_t at;   // offset within the chunk, a multiple of kSumRun
+    uint64_t len;  // <= kSumRun; 0 only for the empty body
+    bool first;    // of the body
+    bool last;     // of the body
+    bool closes;   // the chunk's last run: its slot may be reused once this has run
+};
+
+// How many runs a chunk has.
+inline uint64_t writer_sum_runs_of(const WriterPlan& p, uint64_t chunk) {
+    const uint64_t len = p.chunk_len(chunk);
+    return len == 0 ? 1 : (len - 1) / kSumRun + 1;
+}
+
+// The runs of `chunk` that become due when its uploaded bytes grow from
+// `from` to `to` (from < to <= the chunk's length, or 0 and 0 for the empty
+// body's chunk): those whose last byte lies in [from, to).  In order, to
+// f(run) -> status; stops at the first non-zero status and returns it.
+template <class F>
+int writer_sum_due(const WriterPlan& p, uint64_t chunk, uint64_t from, uint64_t to, F&& f) {
+    const uint64_t len = p.chunk_len(chunk);
+    uint64_t at = from / kSumRun * kSumRun;  // the run that byte `from` lies in
+    for (;;) {
+        // at + kSumRun may pass 2^64 in a chunk that ends near it; len - at does not.
+        const uint64_t end = len - at <= kSumRun ? len : at + kSumRun;
+        if (end > to) return 0;
+        SumRun r;
+        r.chunk = chunk;
+        r.at = at;
+        r.len = end - at;
+        r.first = chunk == 0 && at == 0;
+        r.closes = end == len;
+        r.last = r.closes && chunk + 1 == p.k;
+        if (const int rc = f(r)) return rc;
+        if (r.closes) return 0;
+        at = end;
+    }
 }
 
 }  // namespace mxec

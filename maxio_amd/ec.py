@@ -50,6 +50,9 @@ ERROR_NAMES = {
 DATA_ONLY = 0x1
 # mxec_body_sums_batch flags (include/maxio_ec.h MXEC_SUM_*)
 SUM_MD5, SUM_CRC32, SUM_CRC32C, SUM_SHA1, SUM_SHA256 = 0x01, 0x02, 0x04, 0x08, 0x10
+# mxec_body_sums_update_device (MXEC_SUMS_STATE_BYTES, MXEC_SUMS_F_*)
+SUMS_STATE_BYTES = 512
+SUMS_F_FIRST, SUMS_F_FINAL = 1, 2
 FRAME_CHUNK_SIZE = 65536  # crypto.rs:46
 # mxec_verify / mxec_scrub_object (include/maxio_ec.h MXEC_VERIFY_OK, MXEC_SCRUB_*, MXEC_SHARD_*)
 VERIFY_OK = (1 << 64) - 1
@@ -686,8 +689,9 @@ class Context:
         return ChunkReader(self, ec_dir, offset, length, batch_bytes)
 
     def open_writer(self, ec_dir: str, chunk_size: int, parity_shards: int, total_len: int,
-                    plaintext_size: Optional[int] = None, window_bytes: int = 0) -> "ChunkWriter":
-        return ChunkWriter(self, ec_dir, chunk_size, parity_shards, total_len, plaintext_size, window_bytes)
+                    plaintext_size: Optional[int] = None, window_bytes: int = 0, which: int = 0) -> "ChunkWriter":
+        """which (SUM_*): the body digests ``ChunkWriter.sums()`` returns after finish()."""
+        return ChunkWriter(self, ec_dir, chunk_size, parity_shards, total_len, plaintext_size, window_bytes, which)
 
     def body_sums(self, bodies: Sequence, which: int = 0x1F) -> list[dict]:
         """mxec_body_sums_batch: digests of host bodies (one dict each)."""
@@ -704,6 +708,15 @@ class Context:
         """mxec_body_sums_batch_device: records (76 B each) written to out_ptr."""
         _check(self._lib.mxec_body_sums_batch_device(self._h, dev, stream, _pp(ptrs), _u64p(lens),
                                                      len(ptrs), which, out_ptr))
+
+    def body_sums_update_device(self, ptrs, lens, state_ptr: int, out_ptr: Optional[int], which: int = 0x1F,
+                                flags: int = 0, dev: int = 0, stream=None):
+        """mxec_body_sums_update_device: the next piece of every body (a
+        pointer may be None when its length is 0); body i's state is the
+        SUMS_STATE_BYTES record at state_ptr + i * SUMS_STATE_BYTES, and with
+        SUMS_F_FINAL its 76-byte record goes to out_ptr."""
+        _check(self._lib.mxec_body_sums_update_device(self._h, dev, stream, _pp(ptrs), _u64p(lens), len(ptrs),
+                                                      which, flags, state_ptr, out_ptr))
 
     def put_object_chunked_sums(self, ec_dir: str, chunk_size: int, parity_shards: int, body,
                                 checksum_algo: Optional[str] = None) -> dict:
@@ -942,16 +955,17 @@ class ChunkWriter:
     only closes on an exception (no manifest is written then)."""
 
     def __init__(self, ctx: "Context", ec_dir: str, chunk_size: int, parity_shards: int, total_len: int,
-                 plaintext_size: Optional[int] = None, window_bytes: int = 0):
+                 plaintext_size: Optional[int] = None, window_bytes: int = 0, which: int = 0):
         self._lib = ctx._lib
         self._ctx = ctx  # keeps the device context alive while the writer is open
         self._w = None
         self._finished = False
+        self._which = which
         h = ctypes.c_void_p()
-        _check(self._lib.mxec_writer_open(ctx._h, ec_dir.encode() if ec_dir is not None else None, chunk_size,
-                                          parity_shards, total_len,
-                                          (1 << 64) - 1 if plaintext_size is None else plaintext_size,
-                                          window_bytes, ctypes.byref(h)))
+        _check(self._lib.mxec_writer_open_sums(ctx._h, ec_dir.encode() if ec_dir is not None else None, chunk_size,
+                                               parity_shards, total_len,
+                                               (1 << 64) - 1 if plaintext_size is None else plaintext_size,
+                                               window_bytes, which, ctypes.byref(h)))
         self._w = h
 
     def write(self, data) -> None:
@@ -961,6 +975,14 @@ class ChunkWriter:
     def finish(self) -> None:
         _check(self._lib.mxec_writer_finish(self._w))
         self._finished = True
+
+    def sums(self) -> dict:
+        """mxec_writer_sums: after finish(), the digests of the bytes written
+        that ``which`` named at open, in ``Context.body_sums``' dict shape
+        ({} when which was 0)."""
+        r = N.BodySums()
+        _check(self._lib.mxec_writer_sums(self._w, ctypes.byref(r)))
+        return _sums_dict(r, self._which)
 
     def close(self) -> None:
         if self._w:

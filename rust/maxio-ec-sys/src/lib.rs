@@ -208,6 +208,9 @@ pub const MXEC_SUM_CRC32: u32 = 0x02;
 pub const MXEC_SUM_CRC32C: u32 = 0x04;
 pub const MXEC_SUM_SHA1: u32 = 0x08;
 pub const MXEC_SUM_SHA256: u32 = 0x10;
+pub const MXEC_SUMS_STATE_BYTES: u32 = 512;
+pub const MXEC_SUMS_F_FIRST: u32 = 1;
+pub const MXEC_SUMS_F_FINAL: u32 = 2;
 
 extern "C" {
     pub fn mxec_version() -> *const c_char;
@@ -271,6 +274,8 @@ extern "C" {
     pub fn mxec_frame_aads(ctx: *mut MxecCtx, prefix: *const u8, prefix_len: u32, first_index: u64, n_frames: u64, out: *mut [u8; 32]) -> c_int;
     pub fn mxec_body_sums_batch(ctx: *mut MxecCtx, bodies: *const *const u8, lens: *const u64, n: u64, which: u32, out: *mut MxecBodySums) -> c_int;
     pub fn mxec_body_sums_batch_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, bodies_dev: *const *const u8, lens: *const u64, n: u64, which: u32, out_dev: *mut MxecBodySums) -> c_int;
+    /// `state_dev`: `n` records of `MXEC_SUMS_STATE_BYTES` in device memory (layout private to the library).
+    pub fn mxec_body_sums_update_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, pieces_dev: *const *const u8, lens: *const u64, n: u64, which: u32, flags: u32, state_dev: *mut c_void, out_dev: *mut MxecBodySums) -> c_int;
     pub fn mxec_put_object_chunked_sums(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, body: *const u8, len: usize, which: u32, sums_out: *mut MxecBodySums) -> c_int;
     pub fn mxec_put_object_chunked_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, key: *const u8, nonce_prefix: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, body: *const u8, len: usize, which: u32, sums_out: *mut MxecBodySums) -> c_int;
     pub fn mxec_complete_multipart_chunked(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, parts: *const MxecMultipartPart, n_parts: u32, etag_out: *mut c_char) -> c_int;
@@ -278,8 +283,10 @@ extern "C" {
     pub fn mxec_get_object_chunked(ctx: *mut MxecCtx, ec_dir: *const c_char, offset: u64, length: u64, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
     pub fn mxec_get_object_chunked_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, key: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, frame_size: u32, plaintext_size: u64, offset: u64, length: u64, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
     pub fn mxec_writer_open(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, total_len: u64, plaintext_size: u64, window_bytes: u64, out: *mut *mut c_void) -> c_int;
+    pub fn mxec_writer_open_sums(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, total_len: u64, plaintext_size: u64, window_bytes: u64, which: u32, out: *mut *mut c_void) -> c_int;
     pub fn mxec_writer_write(w: *mut c_void, buf: *const u8, len: u64) -> c_int;
     pub fn mxec_writer_finish(w: *mut c_void) -> c_int;
+    pub fn mxec_writer_sums(w: *mut c_void, out: *mut MxecBodySums) -> c_int;
     pub fn mxec_writer_close(w: *mut c_void);
     pub fn mxec_reader_open(ctx: *mut MxecCtx, ec_dir: *const c_char, offset: u64, length: u64, batch_bytes: u64, out: *mut *mut MxecReader) -> c_int;
     pub fn mxec_reader_read(r: *mut MxecReader, buf: *mut u8, cap: u64) -> i64;

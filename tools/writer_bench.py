@@ -12,7 +12,12 @@ the library allocated for the call, page-locked and pageable alike; the
 caller's body is resident before the note -- then times --reps more PUTs.
 Prints one JSON line per side and one with the ratios.
 
-    python tools/writer_bench.py [--mib 40 --chunk-mib 10 --m 2 --call-mib 1 --reps 7]
+--sums WHICH (MXEC_SUM_* bits, e.g. 1 = MD5): both sides also produce the body
+digests, the writer through mxec_writer_open_sums / mxec_writer_sums, the
+buffered side through mxec_put_object_chunked_sums (MD5 and at most one
+checksum).  The digests are checked against hashlib once, outside the timing.
+
+    python tools/writer_bench.py [--mib 40 --chunk-mib 10 --m 2 --call-mib 1 --reps 7 --sums 0]
 """
 from __future__ import annotations
 
@@ -67,17 +72,26 @@ def side(a) -> None:
             body = ctx.host_array(n)
             body[:] = np.random.default_rng(1).integers(0, 256, n, dtype=np.uint8)
 
+            algo = {0: None, 2: "CRC32", 4: "CRC32C", 8: "SHA1", 16: "SHA256"}.get(a.sums & ~1)
+            last = {}
+
             def put(d, n=n, c=c):
                 t0 = time.perf_counter()
                 if a.side == "buffered":
-                    ctx.put_object_chunked(d, c, a.m, body[:n])
+                    if a.sums:
+                        last["etag"] = ctx.put_object_chunked_sums(d, c, a.m, body[:n], algo)["etag"]
+                    else:
+                        ctx.put_object_chunked(d, c, a.m, body[:n])
                     return time.perf_counter() - t0, 0.0
-                w = ctx.open_writer(d, c, a.m, n)
+                w = ctx.open_writer(d, c, a.m, n, which=a.sums)
                 for o in range(0, n, piece):
                     w.write(body[o:min(n, o + piece)])
                 t1 = time.perf_counter()
                 w.finish()
+                sums = w.sums()
                 w.close()
+                if "md5" in sums:
+                    last["etag"] = '"%s"' % sums["md5"].hex()
                 return time.perf_counter() - t0, time.perf_counter() - t1
 
             put(os.path.join(root, "warm.ec"), n=4 << 16, c=1 << 16)
@@ -90,8 +104,12 @@ def side(a) -> None:
                 wall, tail = put(os.path.join(root, "r%d.ec" % r))
                 walls.append(wall)
                 tails.append(tail)
+            if a.sums & 1:
+                import hashlib
+
+                assert last["etag"] == '"%s"' % hashlib.md5(body.tobytes()).hexdigest(), "ETag mismatch"
             ctx.host_free(body)
-        print(json.dumps({"side": a.side, "body_mib": a.mib, "chunk_mib": a.chunk_mib, "m": a.m,
+        print(json.dumps({"side": a.side, "sums": a.sums, "body_mib": a.mib, "chunk_mib": a.chunk_mib, "m": a.m,
                           "call_mib": a.call_mib, "wall_ms_median": round(1e3 * statistics.median(walls), 2),
                           "wall_ms_min": round(1e3 * min(walls), 2), "wall_ms": [round(1e3 * w, 2) for w in walls],
                           "finish_close_ms_median": round(1e3 * statistics.median(tails), 2),
@@ -109,7 +127,10 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--dir", default=None, help="where the objects are written (default: the temp dir)")
     ap.add_argument("--side", choices=["buffered", "writer"], default=None)
+    ap.add_argument("--sums", type=int, default=0, help="MXEC_SUM_* bits of the body digests both sides produce")
     a = ap.parse_args()
+    if a.sums and a.side != "writer" and (not a.sums & 1 or a.sums & ~1 not in (0, 2, 4, 8, 16)):
+        ap.error("the buffered side takes MD5 plus at most one checksum: --sums 1, 3, 5, 9 or 17")
     if a.side:
         side(a)
         return 0
@@ -117,7 +138,7 @@ def main() -> int:
     for s in ("buffered", "writer"):  # a fresh process each: its own peak
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--side", s, "--mib", str(a.mib),
                             "--chunk-mib", str(a.chunk_mib), "--m", str(a.m), "--call-mib", str(a.call_mib),
-                            "--reps", str(a.reps)] + (["--dir", a.dir] if a.dir else []),
+                            "--reps", str(a.reps), "--sums", str(a.sums)] + (["--dir", a.dir] if a.dir else []),
                            capture_output=True, text=True, timeout=300)
         if r.returncode != 0:
             sys.stderr.write(r.stderr[-4000:])
