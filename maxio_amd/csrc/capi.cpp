@@ -1,145 +1,17 @@
 // capi.cpp — extern "C" entry points of include/maxio_ec.h: context, stats,
-// host memory, SHA-256 batches and the reconstructs (the parity pass, encode /
-// verify / locate, is parity_pass.cpp).  No exception crosses the ABI.
+// page-locked host memory and SHA-256 batches (the parity pass, encode /
+// verify / locate, is parity_pass.cpp; the reconstructs are reconstruct.cpp).
+// No exception crosses the ABI.
 #include <algorithm>
-#include <array>
 #include <cctype>
 #include <fstream>
-#include <cstdio>
-#include <cstdlib>
-#include <unordered_map>
-#include <cstring>
-#include <map>
 #include <string>
-#include <tuple>
-
-#include <sys/syscall.h>
-#include <unistd.h>
 
 #include "../../include/maxio_ec.h"
 #include "kernels.hpp"
 #include "ops.hpp"
 
 using namespace mxec;
-
-namespace {
-
-// One object of a device-resident reconstruct batch (device shard pointers).
-struct BatchObj {
-    int k, m;
-    uint64_t shard_size;
-    uint8_t* const* shards;  // k + m
-    const uint64_t* len;     // k + m, clamped to shard_size
-    uint8_t* present;        // k + m, host
-};
-
-// Rebuilds objects `which` of a batch from their present masks as they stand
-// (chunk_reader.rs:190-211 per object): one decode plan per object, one launch
-// per number of shards to rebuild, shared by objects of every (k, m) and
-// shard size (run_rs_mixed).  Rebuilt shards become present; an object short
-// of k shards gets MXEC_E_TOO_FEW_SHARDS_PRESENT in st.
-int rebuild_batch(Device& d, Slot& slot, hipStream_t s, bool data_only, const std::vector<BatchObj>& all,
-                  const std::vector<uint64_t>& which, std::vector<int32_t>& st) {
-    std::vector<std::shared_ptr<const DecodePlan>> plans(which.size());
-    std::vector<uint32_t> offs(which.size());
-    std::vector<const uint8_t*> in;
-    std::vector<uint8_t*> out;
-    std::vector<uint64_t> il, ol;
-    std::map<int, std::vector<RsMixedObject>> groups;
-    auto collect = [&]() -> int {
-        for (size_t t = 0; t < which.size(); ++t) {
-            const BatchObj& b = all[which[t]];
-            MXEC_TRY(decode_plan(d, b.k, b.m, b.present, data_only, &plans[t], &offs[t]));
-        }
-        return MXEC_OK;
-    };
-    auto launch = [&]() -> int {
-        // Pointer and length tables of every rebuilt object, sized up front
-        // (the RsObjects point into them).
-        size_t n_in = 0, n_out = 0;
-        for (size_t t = 0; t < which.size(); ++t) {
-            st[which[t]] = plans[t] ? MXEC_OK : MXEC_E_TOO_FEW_SHARDS_PRESENT;
-            if (plans[t] && !plans[t]->missing.empty()) {
-                n_in += size_t(all[which[t]].k);
-                n_out += plans[t]->missing.size();
-            }
-        }
-        in.assign(n_in, nullptr);
-        out.assign(n_out, nullptr);
-        il.assign(n_in, 0);
-        ol.assign(n_out, 0);
-        groups.clear();
-        size_t pi = 0, po = 0;
-        for (size_t t = 0; t < which.size(); ++t) {
-            if (!plans[t] || plans[t]->missing.empty()) continue;
-            const BatchObj& b = all[which[t]];
-            const DecodePlan& p = *plans[t];
-            const int r = int(p.missing.size());
-            for (int v = 0; v < b.k; ++v) {
-                in[pi + v] = b.shards[p.valid[size_t(v)]];
-                il[pi + v] = b.len[p.valid[size_t(v)]];
-            }
-            for (int e = 0; e < r; ++e) {
-                out[po + e] = b.shards[p.missing[size_t(e)]];
-                ol[po + e] = b.len[p.missing[size_t(e)]];
-            }
-            groups[r].push_back(RsMixedObject{b.k, b.shard_size, RsObject{&in[pi], &il[pi], &out[po], &ol[po], offs[t]}});
-            pi += size_t(b.k);
-            po += size_t(r);
-        }
-        return run_rs_mixed(d, slot, s, groups);
-    };
-    MXEC_TRY(with_stable_coef(d, s, collect, launch));
-    for (size_t t = 0; t < which.size(); ++t)
-        if (plans[t])
-            for (int e : plans[t]->missing) all[which[t]].present[e] = 1;
-    return MXEC_OK;
-}
-
-// Hashes device shards `ptrs` in one launch on `s` and compares on the device
-// (the verify kernel compares message t against expected_dev[idx[t]]); the
-// flags and the stream form's timeout word are read back, and a mismatch is
-// an erasure: present[idx[t]] = 0 (chunk_reader.rs:176-196).
-int verify_digests_device(Device& d, Slot& slot, hipStream_t s, const std::vector<const uint8_t*>& ptrs,
-                          const std::vector<uint64_t>& lens, const std::vector<uint64_t>& idx,
-                          const uint8_t* expected_dev, uint8_t* present) {
-    MXEC_TRY(slot.digests.grow(ptrs.size()));
-    auto* ok = static_cast<uint8_t*>(slot.digests.p);
-    const uint32_t* tmo = nullptr;
-    MXEC_TRY(run_sha(d, slot, s, ptrs, lens, nullptr, expected_dev, ok, &idx, nullptr, 0, &tmo));
-    const size_t fo = (ptrs.size() + 15) & ~size_t(15);
-    MXEC_TRY(slot.hdig.grow(fo + 16));
-    auto* hflag = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(slot.hdig.p) + fo);
-    *hflag = 0;
-    MXEC_HIP(hipMemcpyAsync(slot.hdig.p, ok, ptrs.size(), hipMemcpyDeviceToHost, s));
-    if (tmo) MXEC_HIP(hipMemcpyAsync(hflag, tmo, 4, hipMemcpyDeviceToHost, s));
-    MXEC_TRY(slot_wait(slot, s));
-    if (*hflag != 0)
-        return set_error(MXEC_E_DEVICE, "SHA-256 stream kernel: a wave timed out waiting for its predecessor segment");
-    const auto* okh = static_cast<const uint8_t*>(slot.hdig.p);
-    for (size_t t = 0; t < idx.size(); ++t)
-        if (!okh[t]) present[idx[t]] = 0;
-    return MXEC_OK;
-}
-
-// The end of a batch reconstruct: every object's status out, and the first
-// failing object's as the call's own, with chunk_reader.rs's message.
-int batch_status(const std::vector<BatchObj>& bo, const std::vector<int32_t>& st, int32_t* status_out) {
-    int first_err = MXEC_OK;
-    for (size_t o = 0; o < bo.size(); ++o) {
-        if (status_out) status_out[o] = st[o];
-        if (st[o] != MXEC_OK && first_err == MXEC_OK) {
-            const int total = bo[o].k + bo[o].m;
-            int np = 0;
-            for (int i = 0; i < total; ++i) np += bo[o].present[i] != 0;
-            first_err = st[o];
-            set_error(first_err, too_few_msg(np, bo[o].k, total));
-        }
-    }
-    return first_err;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -479,268 +351,6 @@ int mxec_sha256_batch(mxec_ctx* ctx, const uint8_t* const* bufs, const size_t* l
         MXEC_TRY(upload_segments(slot, s, base, segs, copy_waves_get(*ds.d)));
         MXEC_TRY(slot_wait(slot, s));  // uploads done: the combiner hashes on its own stream
         return sha256_combined(*ds.d, slot, s, ptrs, l, &out[0][0]);
-    });
-}
-
-int mxec_reconstruct(mxec_ctx* ctx, int k, int m, size_t shard_size, uint8_t* const* shards,
-                     const size_t* shard_len, const uint8_t (*expected_sha256)[32],
-                     uint8_t* present_inout, uint32_t flags, int* n_present) {
-    return guarded([&] {
-        int rc = rs_check(k, m);
-        if (rc) return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
-        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-        if (!shards || !present_inout) return set_error(MXEC_E_INVALID_ARG, "null argument");
-        const int total = k + m;
-        std::vector<uint64_t> len(static_cast<size_t>(total));
-        for (int i = 0; i < total; ++i) {
-            len[size_t(i)] = shard_len ? std::min<uint64_t>(shard_len[i], shard_size) : shard_size;
-            if (!shards[i]) return set_error(MXEC_E_INVALID_ARG, "null shard buffer");
-        }
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, -1));
-        Slot& slot = *ds.slot;
-        hipStream_t s = slot.stream;
-        const uint64_t sa = round_up(shard_size, kSlotAlign);
-        MXEC_TRY(slot.shards.ensure(sa * uint64_t(total) + uint64_t(total) * 64));
-        auto* base = static_cast<uint8_t*>(slot.shards.p);
-        std::vector<uint8_t> present(present_inout, present_inout + total);
-        std::vector<const uint8_t*> sp;
-        std::vector<uint64_t> sl;
-        std::vector<int> si;
-        std::vector<UploadSeg> up;
-        for (int i = 0; i < total; ++i) {
-            if (!present[size_t(i)]) continue;
-            if (len[size_t(i)]) up.push_back({sa * uint64_t(i), shards[i], len[size_t(i)]});
-            sp.push_back(base + sa * uint64_t(i));
-            sl.push_back(len[size_t(i)]);
-            si.push_back(i);
-        }
-        MXEC_TRY(upload_segments(slot, s, base, up, copy_waves_get(*ds.d)));
-        if (expected_sha256 && !sp.empty()) {
-            // chunk_reader.rs:176-196: hash every present shard; mismatch -> erasure.
-            MXEC_TRY(slot_wait(slot, s));
-            std::vector<uint8_t> dig(sp.size() * 32);
-            MXEC_TRY(sha256_combined(*ds.d, slot, s, sp, sl, dig.data()));
-            for (size_t t = 0; t < si.size(); ++t)
-                if (std::memcmp(&dig[t * 32], expected_sha256[si[t]], 32) != 0) present[size_t(si[t])] = 0;
-        }
-        int np = 0;
-        for (int i = 0; i < total; ++i) np += present[size_t(i)] ? 1 : 0;
-        if (n_present) *n_present = np;
-        if (np < k) return set_error(MXEC_E_TOO_FEW_SHARDS_PRESENT, too_few_msg(np, k, total));
-        const bool data_only = (flags & MXEC_F_DATA_ONLY) != 0;
-        std::shared_ptr<const DecodePlan> plan;
-        uint32_t off = 0;
-        std::vector<const uint8_t*> in;
-        std::vector<uint64_t> in_len, out_len;
-        std::vector<uint8_t*> out;
-        auto collect = [&]() -> int {
-            MXEC_TRY(decode_plan(*ds.d, k, m, present.data(), data_only, &plan, &off));
-            if (!plan) return set_error(MXEC_E_SINGULAR_MATRIX, "decode matrix inversion failed");
-            return MXEC_OK;
-        };
-        auto launch = [&]() -> int {
-            if (plan->missing.empty()) return MXEC_OK;
-            in.clear();
-            in_len.clear();
-            out.clear();
-            out_len.clear();
-            for (int v : plan->valid) {
-                in.push_back(base + sa * uint64_t(v));
-                in_len.push_back(len[size_t(v)]);
-            }
-            for (int e : plan->missing) {
-                out.push_back(base + sa * uint64_t(e));
-                out_len.push_back(len[size_t(e)]);
-            }
-            RsObject ob{in.data(), in_len.data(), out.data(), out_len.data(), off};
-            return run_rs(*ds.d, slot, s, shard_size, k, int(out.size()), {ob});
-        };
-        MXEC_TRY(with_stable_coef(*ds.d, s, collect, launch));
-        if (!plan->missing.empty()) {
-            std::vector<DownloadSeg> down;
-            for (size_t t = 0; t < out.size(); ++t)
-                if (out_len[t]) down.push_back({sa * uint64_t(plan->missing[t]), shards[plan->missing[t]], out_len[t]});
-            // plan->missing is ascending, so are the offsets.
-            MXEC_TRY(download_segments(slot, s, base, down, copy_waves_get(*ds.d)));
-            for (int e : plan->missing) present[size_t(e)] = 1;
-        } else {
-            // Nothing to rebuild: the uploads may still be reading the
-            // caller's buffers (direct DMA from page-locked memory).
-            MXEC_TRY(slot_wait(slot, s));
-        }
-        std::memcpy(present_inout, present.data(), size_t(total));
-        return MXEC_OK;
-    });
-}
-
-int mxec_reconstruct_strided_device(mxec_ctx* ctx, int dev, void* stream, int k, int m,
-                                    uint64_t shard_size, uint64_t n_obj, uint8_t* shards,
-                                    uint64_t obj_stride, uint64_t shard_stride,
-                                    const uint64_t* shard_len, uint8_t* present,
-                                    const uint8_t* expected_sha_dev, uint32_t flags,
-                                    int32_t* status_out) {
-    return guarded([&] {
-        int rc = rs_check(k, m);
-        if (rc) return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
-        if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-        if (n_obj == 0) return MXEC_OK;
-        if (!shards || !present) return set_error(MXEC_E_INVALID_ARG, "null argument");
-        const int total = k + m;
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, dev));
-        Slot& slot = *ds.slot;
-        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-        std::vector<uint64_t> len(static_cast<size_t>(total));
-        for (int i = 0; i < total; ++i)
-            len[size_t(i)] = shard_len ? std::min<uint64_t>(shard_len[i], shard_size) : shard_size;
-        auto shard_ptr = [&](uint64_t o, int i) { return shards + o * obj_stride + uint64_t(i) * shard_stride; };
-        const bool data_only = (flags & MXEC_F_DATA_ONLY) != 0;
-        std::vector<int32_t> st(static_cast<size_t>(n_obj), MXEC_OK);
-        std::vector<uint8_t*> sp(static_cast<size_t>(n_obj * total));
-        std::vector<BatchObj> bo(static_cast<size_t>(n_obj));
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            for (int i = 0; i < total; ++i) sp[o * total + i] = shard_ptr(o, i);
-            bo[o] = BatchObj{k, m, shard_size, &sp[o * total], len.data(), present + o * total};
-        }
-        // Rebuild `objs` from the present mask as it stands (rebuild_batch).
-        auto rebuild = [&](const std::vector<uint64_t>& objs) -> int {
-            return rebuild_batch(*ds.d, slot, s, data_only, bo, objs, st);
-        };
-        std::vector<uint64_t> all(static_cast<size_t>(n_obj));
-        for (uint64_t o = 0; o < n_obj; ++o) all[o] = o;
-        bool rebuilt = false;
-        if (expected_sha_dev) {
-            std::vector<const uint8_t*> ptrs;
-            std::vector<uint64_t> lens;
-            std::vector<uint64_t> idx;
-            for (uint64_t o = 0; o < n_obj; ++o)
-                for (int i = 0; i < total; ++i)
-                    if (present[o * total + i]) {
-                        ptrs.push_back(shard_ptr(o, i));
-                        lens.push_back(len[size_t(i)]);
-                        idx.push_back(o * total + i);
-                    }
-            if (!ptrs.empty() && !sha_combines(*ds.d, ptrs.size())) {
-                // A batch that fills the chip: its own launch on `stream`,
-                // digests compared on the device (the verify kernel compares
-                // message t against expected[idx[t]]), n flags read back.
-                MXEC_TRY(verify_digests_device(*ds.d, slot, s, ptrs, lens, idx, expected_sha_dev, present));
-            } else if (!ptrs.empty()) {
-                // A small batch: hashed by the device's combiner together with
-                // every concurrent caller's verification (combiner.cpp), once
-                // the work queued on `stream` has produced the shards; digests
-                // compared on the host.  The combined launch waits for that
-                // work on the device (an event recorded here), not the host.
-                //
-                // Speculative rebuild: the decode from the present mask as
-                // given is queued right behind that event, so it runs beside
-                // the hash instead of after it (the hash is a VALU-bound
-                // chain, the decode an HBM stream).  It reads only present
-                // shards and writes only missing ones, which the hash does not
-                // read.  Objects whose digests all match keep it -- exactly
-                // what verify-then-rebuild produces; an object with a
-                // mismatch is rebuilt again from its original mask minus the
-                // mismatched shards, over the same output shards, in stream
-                // order (chunk_reader.rs:176-211 semantics).  An object that
-                // ends up short of k shards may have its missing shards
-                // overwritten by the speculative decode.
-                const size_t ne = size_t(n_obj) * size_t(total) * 32;
-                MXEC_TRY(slot.hdig.grow(ne));
-                MXEC_HIP(hipMemcpyAsync(slot.hdig.p, expected_sha_dev, ne, hipMemcpyDeviceToHost, s));
-                if (!slot.ready_ev) MXEC_HIP(hipEventCreateWithFlags(&slot.ready_ev, hipEventDisableTiming));
-                MXEC_HIP(hipEventRecord(slot.ready_ev, s));
-                const std::vector<uint8_t> orig(present, present + n_obj * uint64_t(total));
-                // Queued by the combiner's leader right after the hash launch,
-                // so the host work of the plans does not hold back the hash
-                // (or this caller's arrival with it).
-                const std::function<int()> spec = [&] { return rebuild(all); };
-                rebuilt = true;
-                std::vector<uint8_t> dig(ptrs.size() * 32);
-                if (int hrc = sha256_combined(*ds.d, slot, s, ptrs, lens, dig.data(), slot.ready_ev, &spec)) {
-                    // No verdict: the mask goes back as it came (the speculative
-                    // rebuild may already have marked shards present).
-                    const std::string msg = last_error();
-                    std::memcpy(present, orig.data(), orig.size());
-                    (void)slot_wait(*ds.slot, s);  // the speculative decode, if queued
-                    return set_error(hrc, msg);
-                }
-                MXEC_TRY(slot_wait(*ds.slot, s));  // the digest copy (long done), the speculative decode
-                const auto* exph = static_cast<const uint8_t*>(slot.hdig.p);
-                std::vector<uint64_t> redo;
-                for (size_t t = 0; t < idx.size(); ++t) {
-                    if (std::memcmp(&dig[t * 32], exph + idx[t] * 32, 32) == 0) continue;
-                    const uint64_t o = idx[t] / uint64_t(total);
-                    if (redo.empty() || redo.back() != o) {
-                        redo.push_back(o);  // idx ascends: objects arrive in order
-                        std::memcpy(present + o * total, &orig[o * total], size_t(total));
-                    }
-                }
-                for (size_t t = 0; t < idx.size(); ++t)
-                    if (std::memcmp(&dig[t * 32], exph + idx[t] * 32, 32) != 0) present[idx[t]] = 0;
-                MXEC_TRY(rebuild(redo));
-            }
-        }
-        if (!rebuilt) MXEC_TRY(rebuild(all));
-        return batch_status(bo, st, status_out);
-    });
-}
-
-int mxec_reconstruct_batch_device(mxec_ctx* ctx, int dev, void* stream, const mxec_object* objs,
-                                  uint64_t n_obj, uint8_t* const* shards, const uint64_t* shard_len,
-                                  uint8_t* present, const uint8_t* expected_sha_dev, uint32_t flags,
-                                  int32_t* status_out) {
-    return guarded([&] {
-        if (n_obj == 0) return MXEC_OK;
-        if (!objs || !shards || !present) return set_error(MXEC_E_INVALID_ARG, "null argument");
-        std::vector<uint64_t> first(static_cast<size_t>(n_obj));
-        uint64_t sum = 0;
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            if (int rc = rs_check(objs[o].k, objs[o].m))
-                return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
-            if (objs[o].shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
-            first[o] = sum;
-            sum += uint64_t(objs[o].k + objs[o].m);
-        }
-        DevScope ds;
-        MXEC_TRY(ds.open(ctx, dev));
-        Slot& slot = *ds.slot;
-        hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = the HIP null stream
-        // Every shard pointer is needed: present ones are read, missing ones
-        // are where the rebuilt bytes go (a NULL would fault the device).
-        for (uint64_t g = 0; g < sum; ++g)
-            if (!shards[g]) return set_error(MXEC_E_INVALID_ARG, "null shard pointer " + std::to_string(g));
-        std::vector<uint64_t> len(static_cast<size_t>(sum));
-        std::vector<BatchObj> bo(static_cast<size_t>(n_obj));
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            const uint64_t S = objs[o].shard_size;
-            for (int i = 0; i < objs[o].k + objs[o].m; ++i) {
-                const uint64_t g = first[o] + uint64_t(i);
-                len[g] = shard_len ? std::min<uint64_t>(shard_len[g], S) : S;
-            }
-            bo[o] = BatchObj{objs[o].k, objs[o].m, S, shards + first[o], &len[first[o]], present + first[o]};
-        }
-        if (expected_sha_dev) {
-            // Verify every present shard in one launch on `stream` (digests
-            // compared on the device against expected[global shard index]),
-            // read the flags back; a mismatch is an erasure
-            // (chunk_reader.rs:176-196).
-            std::vector<const uint8_t*> ptrs;
-            std::vector<uint64_t> lens, idx;
-            for (uint64_t g = 0; g < sum; ++g)
-                if (present[g]) {
-                    ptrs.push_back(shards[g]);
-                    lens.push_back(len[g]);
-                    idx.push_back(g);
-                }
-            if (!ptrs.empty())
-                MXEC_TRY(verify_digests_device(*ds.d, slot, s, ptrs, lens, idx, expected_sha_dev, present));
-        }
-        std::vector<int32_t> st(static_cast<size_t>(n_obj), MXEC_OK);
-        std::vector<uint64_t> all(static_cast<size_t>(n_obj));
-        for (uint64_t o = 0; o < n_obj; ++o) all[o] = o;
-        MXEC_TRY(rebuild_batch(*ds.d, slot, s, (flags & MXEC_F_DATA_ONLY) != 0, bo, all, st));
-        return batch_status(bo, st, status_out);
     });
 }
 

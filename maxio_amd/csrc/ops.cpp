@@ -1,7 +1,6 @@
 // ops.cpp — kernel launches over device pointers: the RS launches planned by
 // rs_plan.hpp, the grid tuner, the coefficient lookups, the SHA-256 launches.
 #include <cstdlib>
-#include <cstring>
 
 #include "ops.hpp"
 
@@ -25,6 +24,12 @@ int check_km(int k, int m) {
     if (k + m > 255) return too_many_shards(uint64_t(k), uint64_t(m));
     int rc = rs_check(k, m);
     if (rc) return set_error(rc, std::string("Reed-Solomon init error: ") + mxec_strerror(rc));
+    return MXEC_OK;
+}
+
+int reconstruct_shape(int k, int m, uint64_t shard_size) {
+    if (int rc = rs_check(k, m)) return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
+    if (shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
     return MXEC_OK;
 }
 
@@ -100,6 +105,28 @@ int decode_plan(Device& dev, int k, int m, const uint8_t* present, bool data_onl
     *plan = p;
     *off = o;
     return MXEC_OK;
+}
+
+int decode_step(Device& dev, Slot& slot, hipStream_t s, std::vector<DecodeItem> items, bool data_only,
+                std::vector<std::shared_ptr<const DecodePlan>>& plans, uint64_t off, uint64_t pw, DescArena* arena,
+                uint32_t max_blocks) {
+    plans.assign(items.size(), nullptr);
+    DecodeTables tables;
+    auto collect = [&]() -> int {
+        for (size_t t = 0; t < items.size(); ++t) {
+            DecodeItem& it = items[t];
+            if (it.S > off) MXEC_TRY(decode_plan(dev, it.k, it.m, it.present, data_only, &plans[t], &it.coef_off));
+            it.plan = plans[t].get();
+        }
+        return MXEC_OK;
+    };
+    // The tables are rebuilt on every run: a re-run after a recycle of the
+    // coefficient arena carries the fresh offsets.
+    auto launch = [&]() -> int {
+        const auto groups = tables.build(items, off, pw);
+        return groups.empty() ? MXEC_OK : run_rs_mixed(dev, slot, s, groups, arena, max_blocks);
+    };
+    return with_stable_coef(dev, s, collect, launch);
 }
 
 namespace {

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "decode_tables.hpp"
 #include "gf256.hpp"
 #include "rs_plan.hpp"
 #include "runtime.hpp"
@@ -107,6 +108,15 @@ int decode_coef(Device& dev, const DecodePlan& plan, bool data_only, uint32_t* o
 int decode_plan(Device& dev, int k, int m, const uint8_t* present, bool data_only,
                 std::shared_ptr<const DecodePlan>* plan, uint32_t* off);
 
+// The decode launch of every reconstruct: bytes [off, off + pw) of each
+// item's missing shards from its decode plan (looked up from its present
+// flags as they stand; none for an item short of k shards or with S <= off),
+// in one grouped launch on s (decode_tables.hpp, run_rs_mixed with `arena`
+// and `max_blocks`), under with_stable_coef.  plans[t] is item t's plan.
+int decode_step(Device& dev, Slot& slot, hipStream_t s, std::vector<DecodeItem> items, bool data_only,
+                std::vector<std::shared_ptr<const DecodePlan>>& plans, uint64_t off = 0,
+                uint64_t pw = ~uint64_t(0), DescArena* arena = nullptr, uint32_t max_blocks = 0);
+
 // Host-API staging: shard slots are this many bytes apart on the device.
 constexpr uint64_t kSlotAlign = 256;
 inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
@@ -202,6 +212,32 @@ inline std::string too_few_msg(int present, int k, int total) {
     return "too many missing/corrupt shards: only " + std::to_string(present) + " of " +
            std::to_string(k) + " required shards available (" + std::to_string(total - present) +
            " missing)";
+}
+
+// The shape check of every reconstruct: the crate's ReedSolomon::new checks,
+// then its empty-shard error.
+int reconstruct_shape(int k, int m, uint64_t shard_size);
+
+// The end of a batch reconstruct: every object's status out, and the first
+// failing object's as the call's own, with chunk_reader.rs's message.
+// objs[o].k / .m: the objects' shapes; present: their flags, one object after
+// another.
+template <class Obj>
+int reconstruct_status(const Obj* objs, uint64_t n_obj, const uint8_t* present, const std::vector<int32_t>& st,
+                       int32_t* status_out) {
+    int first_err = MXEC_OK;
+    for (uint64_t o = 0; o < n_obj; ++o) {
+        const int total = objs[o].k + objs[o].m;
+        if (status_out) status_out[o] = st[o];
+        if (st[o] != MXEC_OK && first_err == MXEC_OK) {
+            int np = 0;
+            for (int i = 0; i < total; ++i) np += present[i] != 0;
+            first_err = st[o];
+            set_error(first_err, too_few_msg(np, objs[o].k, total));
+        }
+        present += total;
+    }
+    return first_err;
 }
 
 // Coefficient-table offsets are valid while their generation's half of the

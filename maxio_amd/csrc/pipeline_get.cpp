@@ -3,7 +3,6 @@
 // missing ones rebuilt into host memory, the present ones verified against
 // their digests on the way), spread over every device of the context
 // (pipeline.hpp).
-#include <map>
 #include <memory>
 
 #include "pipeline.hpp"
@@ -299,66 +298,19 @@ private:
     // The decode of bytes [off, off + pw) of objects `which`: each object's
     // missing shards from its decode plan (plans[t]; none when it is short
     // of k shards or ends before off), in one grouped launch on s
-    // (run_rs_mixed; blocks: its workgroup cap, 0 = the default grid).  RS
-    // is bytewise, so a piece of the output comes from the same piece of the
-    // inputs, as in the PUT's piece-major encode; a whole-shard rebuild is
-    // off 0, pw unbounded.
+    // (decode_step over the pool's slots; blocks: its workgroup cap, 0 = the
+    // default grid).  A whole-shard rebuild is off 0, pw unbounded.
     int decode_piece(const std::vector<RecObj>& objs, const std::vector<size_t>& which, uint64_t off, uint64_t pw,
                      bool data_only, hipStream_t s, uint32_t blocks,
                      std::vector<std::shared_ptr<const DecodePlan>>& plans) {
         uint8_t* base = static_cast<uint8_t*>(pool_.p);
-        const size_t n = which.size();
-        plans.assign(n, nullptr);
-        std::vector<uint32_t> offs(n);
-        std::vector<const uint8_t*> in;
-        std::vector<uint8_t*> out;
-        std::vector<uint64_t> il, ol;
-        std::map<int, std::vector<RsMixedObject>> rs_groups;
-        auto collect = [&]() -> int {
-            for (size_t t = 0; t < n; ++t) {
-                const RecObj& h = objs[which[t]];
-                plans[t].reset();
-                if (h.S > off) MXEC_TRY(decode_plan(d_, h.k, h.m, h.present, data_only, &plans[t], &offs[t]));
-            }
-            return MXEC_OK;
-        };
-        auto launch = [&]() -> int {
-            size_t n_in = 0, n_out = 0;
-            for (size_t t = 0; t < n; ++t)
-                if (plans[t] && !plans[t]->missing.empty()) {
-                    n_in += size_t(objs[which[t]].k);
-                    n_out += plans[t]->missing.size();
-                }
-            in.assign(n_in, nullptr);
-            out.assign(n_out, nullptr);
-            il.assign(n_in, 0);
-            ol.assign(n_out, 0);
-            rs_groups.clear();
-            size_t pi = 0, po = 0;
-            for (size_t t = 0; t < n; ++t) {
-                if (!plans[t] || plans[t]->missing.empty()) continue;
-                const RecObj& h = objs[which[t]];
-                const DecodePlan& p = *plans[t];
-                const int r = int(p.missing.size());
-                uint8_t* ob = base + h.pool_off + off;
-                for (int v = 0; v < h.k; ++v) {
-                    const uint64_t L = h.len[p.valid[size_t(v)]];
-                    in[pi + v] = ob + uint64_t(p.valid[size_t(v)]) * h.slot();
-                    il[pi + v] = L > off ? std::min(pw, L - off) : 0;
-                }
-                for (int e = 0; e < r; ++e) {
-                    const uint64_t L = h.len[p.missing[size_t(e)]];
-                    out[po + e] = ob + uint64_t(p.missing[size_t(e)]) * h.slot();
-                    ol[po + e] = L > off ? std::min(pw, L - off) : 0;
-                }
-                rs_groups[r].push_back(RsMixedObject{h.k, std::min(pw, h.S - off),
-                                                     RsObject{&in[pi], &il[pi], &out[po], &ol[po], offs[t]}});
-                pi += size_t(h.k);
-                po += size_t(r);
-            }
-            return rs_groups.empty() ? MXEC_OK : run_rs_mixed(d_, slot_, s, rs_groups, &arena_, blocks);
-        };
-        return with_stable_coef(d_, s, collect, launch);
+        std::vector<DecodeItem> items;
+        items.reserve(which.size());
+        for (size_t o : which) {
+            const RecObj& h = objs[o];
+            items.push_back(DecodeItem{h.k, h.m, h.S, h.len, h.present, nullptr, base + h.pool_off, h.slot()});
+        }
+        return decode_step(d_, slot_, s, std::move(items), data_only, plans, off, pw, &arena_, blocks);
     }
 
     // Objects `which` of a wave, their present shards up (or verified):
@@ -613,9 +565,7 @@ extern "C" int mxec_reconstruct_batch_host(mxec_ctx* ctx, const mxec_object* obj
         if (!D) return set_error(MXEC_E_NO_DEVICE, "context has no device");
         uint64_t sum = 0;
         for (uint64_t o = 0; o < n_obj; ++o) {
-            if (int rc = rs_check(objs[o].k, objs[o].m))
-                return set_error(rc, std::string("RS init error: ") + mxec_strerror(rc));
-            if (objs[o].shard_size == 0) return set_error(MXEC_E_EMPTY_SHARD, mxec_strerror(MXEC_E_EMPTY_SHARD));
+            MXEC_TRY(reconstruct_shape(objs[o].k, objs[o].m, objs[o].shard_size));
             sum += uint64_t(objs[o].k + objs[o].m);
         }
         // Every shard pointer is needed: present ones are read, missing ones
@@ -648,20 +598,7 @@ extern "C" int mxec_reconstruct_batch_host(mxec_ctx* ctx, const mxec_object* obj
         MXEC_TRY(for_each_device(ctx->c, per, [&](Device& dev, PipeHub& hub, PipeLane& lane, std::vector<RecObj>& mine) {
             return GetCall(dev, hub, lane).run(mine, data_only);
         }));
-        int first_err = MXEC_OK;
-        g0 = 0;
-        for (uint64_t o = 0; o < n_obj; ++o) {
-            const int total = objs[o].k + objs[o].m;
-            if (status_out) status_out[o] = st[o];
-            if (st[o] != MXEC_OK && first_err == MXEC_OK) {
-                int np = 0;
-                for (int i = 0; i < total; ++i) np += present[g0 + uint64_t(i)] != 0;
-                first_err = st[o];
-                set_error(first_err, too_few_msg(np, objs[o].k, total));
-            }
-            g0 += uint64_t(total);
-        }
-        return first_err;
+        return reconstruct_status(objs, n_obj, present, st, status_out);
     } catch (const std::bad_alloc&) {
         return set_error(MXEC_E_OOM, "host allocation failed");
     } catch (const std::exception& e) {

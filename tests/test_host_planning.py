@@ -15,7 +15,11 @@
   uniform, unaligned, grouped, verify / locate and multi-r launches so that a
   walk of each launch meets every (object, tile) once on that object's
   entries, and splits a mixed call into grouped, uniform and multi-r launches
-  by its alignment, uniformity and 32-bit rules (rs_plan.hpp)."""
+  by its alignment, uniformity and 32-bit rules (rs_plan.hpp);
+* the reconstructs' decode table builder puts every object with shards to
+  rebuild exactly once under its number of rebuilt shards, its rows inside the
+  returned tables with the windowed pointers, lengths and shard size, for both
+  shard-location forms (decode_tables.hpp)."""
 from __future__ import annotations
 
 import os
@@ -31,7 +35,8 @@ HERE = os.path.join(ROOT, "tests", "c_manifest")
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 @pytest.mark.parametrize("src,ok", [("sha_guard_check.cpp", "sha guard ok"), ("deal_check.cpp", "deal ok"),
                                     ("piece_grid_check.cpp", "piece grid ok"), ("wave_cut_check.cpp", "wave cut ok"),
-                                    ("rs_plan_check.cpp", "rs plan ok")])
+                                    ("rs_plan_check.cpp", "rs plan ok"),
+                                    ("decode_tables_check.cpp", "decode tables ok")])
 def test_host_planning(tmp_path, src, ok):
     exe = str(tmp_path / src.split(".")[0])
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
