@@ -614,6 +614,34 @@ int mxec_frames_encrypt_device(mxec_ctx* ctx, int dev, void* stream,
 int mxec_frames_decrypt_device(mxec_ctx* ctx, int dev, void* stream,
                                const mxec_frames_job* jobs, uint64_t n_jobs,
                                int32_t* status_out);
+/* The encrypt form whose destination is a ring of chunk slots instead of one
+ * contiguous run: FrameEncryptor (crypto.rs:94-117) writing straight into the
+ * chunks put_object_chunked_encrypted's loop cuts its output into
+ * (filesystem.rs:835-1060).  Byte x of the frame stream is stored at
+ *     base_dev + ((x / chunk_size) % slots) * slot_stride + x % chunk_size.
+ * One job per call; job->out_dev is ignored.  stream_off is the frame-stream
+ * offset of the job's first frame and may take any value.  A frame's nonce,
+ * ciphertext and tag may each be cut by chunk boundaries, any number of times,
+ * and by the ring's wrap.  Bytes of the window outside the mapped range (the
+ * slot_stride - chunk_size gaps, the other slots) are never written.
+ * Enqueue-only on `stream`.  MXEC_E_INVALID_ARG, decided before anything is
+ * queued: a null job, win, key, base_dev, in_dev with len > 0 or aad_dev with
+ * aad_len > 0; a frame_size that is 0, no multiple of 16 or above 2^31 - 256;
+ * chunk_size == 0; slot_stride < chunk_size; slots == 0 or a window of 2^62
+ * bytes or more; a job whose stream bytes (mxec_frames_len) span more than
+ * slots * chunk_size, for it would overwrite itself.  len == 0 is MXEC_OK and
+ * does nothing.  `win` points at a mxec_frames_window, passed as const void*
+ * (as mxec_scrub_object passes its report). */
+struct mxec_frames_window {
+    uint8_t* base_dev;      /* slot 0 */
+    uint64_t chunk_size;    /* frame-stream bytes per chunk, > 0 */
+    uint64_t slot_stride;   /* >= chunk_size */
+    uint64_t slots;         /* >= 1; chunk j lives in slot j % slots */
+};
+typedef struct mxec_frames_window mxec_frames_window;
+int mxec_frames_encrypt_window_device(mxec_ctx* ctx, int dev, void* stream,
+                                      const mxec_frames_job* job, uint64_t stream_off,
+                                      const void* win);
 /* build_frame_aad / build_part_aad (filesystem.rs:118-158): out[i] =
  * SHA-256(prefix || (first_index + i) as u64 LE), prefix = the identity bytes
  * (bucket 0 key 0 version 0, or "PART" 0 upload_id 0 part_le4 0). */
@@ -791,7 +819,44 @@ int mxec_complete_multipart_chunked_encrypted(mxec_ctx* ctx, const char* ec_dir,
  * digests, not the plaintext's as mxec_put_object_chunked_encrypted returns.
  * One lone fast body pays for them: its wall time becomes the slowest
  * requested chain's (MD5: about 13 ns per byte against 1.1 on a CPU core);
- * they pay with many bodies in flight. */
+ * they pay with many bodies in flight.
+ *
+ * mxec_writer_open_encrypted (put_object_chunked_encrypted,
+ * filesystem.rs:835-1060, as a push stream; FrameEncryptor, crypto.rs:94-117):
+ * the caller writes plaintext, exactly plaintext_len bytes in pieces of any
+ * size, and the writer encrypts.  The frame stream has
+ * mxec_frames_len(plaintext_len, 65536) bytes: k, the chunk lengths and the
+ * shard-count guards come from that length, decided here before anything is
+ * created.  Frames are 65536 bytes with first index 0, frame i's AAD =
+ * SHA-256(aad_prefix || i as u64 LE) (build_frame_aad, filesystem.rs:118-128).
+ * After finish, ec_dir holds byte for byte what
+ * mxec_put_object_chunked_encrypted writes for the concatenated body:
+ * total_size = frame-stream bytes, plaintext_size = plaintext_len; an empty
+ * body is one empty chunk, no parity, plaintext_size 0.  `which` /
+ * mxec_writer_sums give the digests of the plaintext, as the buffered call
+ * does.  mxec_writer_write, _finish, _sums and _close take the handle
+ * unchanged; the error contract is the plain writer's, the over-run and
+ * short-finish texts in plaintext bytes.  A null key or nonce_prefix, or
+ * aad_prefix_len without aad_prefix, is MXEC_E_INVALID_ARG, as is a
+ * plaintext_len whose frame stream does not fit in 64 bits.
+ * Data path: plaintext goes through the staging pieces into a ring of four
+ * 1 MiB stretches in HBM, not into the window, and the digest runs read it
+ * there.  With a stretch's last byte (or the body's) one launch of the GCM
+ * kernel's window form (mxec_frames_encrypt_window_device) encrypts its 16
+ * frames straight into the chunk slots, behind the upload: one launch per MiB
+ * however small the writes are.  Its AADs are hashed on the host and go up in
+ * front of it; the key schedule and GHASH tables are prepared once at open and
+ * stay in HBM until close, when the host copies of key and tables are zeroed.
+ * The ciphertext comes down through two more page-locked pieces (at most
+ * 1 MiB each) and goes to the chunk files a piece or two behind the encrypt;
+ * finish() drains them.  A completed ciphertext chunk is hashed and folded as
+ * in the plain writer.  A stretch is reused once its launch and digest run
+ * have finished, a slot once its chunk's hash, fold and download have.
+ * window_bytes: as above, but never fewer slots than one launch's
+ * 1 049 024 stream bytes touch (ceil(1 049 024 / chunk_size) + 1, or all k).
+ * Memory: host, four page-locked pieces and the manifest's entries; HBM, the
+ * window, 2 * m * chunk_size of parity, the 4 MiB plaintext ring and 12.6 KiB
+ * of key tables.  None grows with plaintext_len. */
 typedef struct mxec_writer mxec_writer;
 int mxec_writer_open(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size,
                      uint32_t parity_shards, uint64_t total_len, uint64_t plaintext_size,
@@ -799,6 +864,11 @@ int mxec_writer_open(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size,
 int mxec_writer_open_sums(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size,
                           uint32_t parity_shards, uint64_t total_len, uint64_t plaintext_size,
                           uint64_t window_bytes, uint32_t which, void** out);
+int mxec_writer_open_encrypted(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size,
+                               uint32_t parity_shards, uint64_t plaintext_len,
+                               const uint8_t key[32], const uint8_t nonce_prefix[4],
+                               const uint8_t* aad_prefix, uint32_t aad_prefix_len,
+                               uint64_t window_bytes, uint32_t which, void** out);
 int mxec_writer_write(void* w, const uint8_t* buf, uint64_t len);
 int mxec_writer_finish(void* w);
 int mxec_writer_sums(void* w, mxec_body_sums* out);

@@ -52,6 +52,17 @@ class FramesJob(ctypes.Structure):
     ]
 
 
+class FramesWindow(ctypes.Structure):
+    """mxec_frames_window: the ring of chunk slots of mxec_frames_encrypt_window_device."""
+
+    _fields_ = [
+        ("base_dev", ctypes.c_void_p),
+        ("chunk_size", ctypes.c_uint64),
+        ("slot_stride", ctypes.c_uint64),
+        ("slots", ctypes.c_uint64),
+    ]
+
+
 class ChunkInfo(ctypes.Structure):
     """mxec_chunk_info == the reference's ChunkInfo (storage/mod.rs:182-189)."""
 
@@ -198,6 +209,7 @@ _SIGS = {
     "mxec_frames_encrypt": (INT, [P, P, P, U64, P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, U64P]),
     "mxec_frames_decrypt": (INT, [P, P, U64, P, ctypes.c_uint32, ctypes.c_uint32, P, U64, U64, P, U64, U64P]),
     "mxec_frames_encrypt_device": (INT, [P, INT, P, P, U64]),
+    "mxec_frames_encrypt_window_device": (INT, [P, INT, P, P, U64, P]),
     "mxec_frames_decrypt_device": (INT, [P, INT, P, P, U64, ctypes.POINTER(ctypes.c_int32)]),
     "mxec_frame_aads": (INT, [P, P, ctypes.c_uint32, U64, U64, P]),
     "mxec_body_sums_batch_device": (INT, [P, INT, P, PP, U64P, U64, ctypes.c_uint32, P]),
@@ -210,6 +222,8 @@ _SIGS = {
                                ctypes.POINTER(ctypes.c_void_p)]),
     "mxec_writer_open_sums": (INT, [P, ctypes.c_char_p, U64, ctypes.c_uint32, U64, U64, U64, ctypes.c_uint32,
                                     ctypes.POINTER(ctypes.c_void_p)]),
+    "mxec_writer_open_encrypted": (INT, [P, ctypes.c_char_p, U64, ctypes.c_uint32, U64, P, P, P, ctypes.c_uint32, U64,
+                                         ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
     "mxec_writer_write": (INT, [P, P, U64]),
     "mxec_writer_finish": (INT, [P]),
     "mxec_writer_sums": (INT, [P, P]),

@@ -124,7 +124,10 @@ Blk mul_table(const Blk t[32][16], const Blk& x) {
     return z;
 }
 
-void build_key(const uint8_t key[32], GcmKey& k) {
+}  // namespace
+
+// A data key's tables (kernels.hpp GcmKey); ops.hpp declares it.
+void mxec::gcm_prepare_key(const uint8_t key[32], GcmKey& k) {
     expand_key(key, k.rk);
     uint8_t h8[16] = {0};
     aes_block_host(k.rk, h8);
@@ -143,6 +146,8 @@ void build_key(const uint8_t key[32], GcmKey& k) {
         for (int v = 0; v < 16; ++v)
             for (int q = 0; q < 4; ++q) k.htab[a][v][q] = th[a][v][q];
 }
+
+namespace {
 
 int te_tables(Device& d, const uint32_t** out) {
     std::lock_guard<std::mutex> g(d.sums_mu);
@@ -170,29 +175,53 @@ struct Job {
     uint8_t* out;        // device: frames (encrypt) / plaintext (decrypt)
 };
 
+// Where a launch's frames go when not to Job::out: the chunk ring of
+// mxec_frames_window, `off` the stream offset of the (one) job's first frame.
+struct Window {
+    mxec_frames_window w;
+    uint64_t off;
+};
+
 // One launch over every frame of every job; decrypt statuses per frame land
-// in status_dev.
+// in status_dev.  keys_dev: the jobs' GcmKeys already resident in HBM, one
+// per job (null: prepared here from Job::key and uploaded with the frames).
+// win (encrypt, one job): the window form.  arena: the tables from it instead
+// of the slot's ring, whose entries are fenced by events on `s` -- a caller
+// whose stream does not outlive the slot (a writer's) brings its own.
 int run_frames(Device& d, Slot& slot, hipStream_t s, const std::vector<Job>& jobs, bool decrypt,
-               int32_t* status_dev) {
+               int32_t* status_dev, const GcmKey* keys_dev = nullptr, const Window* win = nullptr,
+               DescArena* arena = nullptr) {
     std::vector<GcmFrame> frames;
-    std::vector<GcmKey> keys(jobs.size());
+    std::vector<GcmKey> keys(keys_dev ? 0 : jobs.size());
+    // The window mapping has period slots * chunk_size: the launch is rebased
+    // into its first two periods (kernels.hpp GcmWinArgs).
+    uint64_t pos0 = 0;
+    if (win) {
+        const uint64_t chunk = win->off / win->w.chunk_size;
+        pos0 = (chunk % win->w.slots) * win->w.chunk_size + (win->off - chunk * win->w.chunk_size);
+    }
     for (size_t j = 0; j < jobs.size(); ++j) {
         const Job& jb = jobs[j];
-        build_key(jb.key, keys[j]);
+        if (!keys_dev) gcm_prepare_key(jb.key, keys[j]);
         const uint64_t nf = n_frames(jb.len, jb.frame_size);
         const uint64_t fl = uint64_t(jb.frame_size) + MXEC_FRAME_OVERHEAD;
         for (uint64_t f = 0; f < nf; ++f) {
             GcmFrame fr{};
             const uint64_t plen = std::min<uint64_t>(jb.frame_size, jb.len - f * jb.frame_size);
-            uint8_t* frame = const_cast<uint8_t*>(decrypt ? jb.in : jb.out) + f * fl;
-            fr.hdr = frame;
-            fr.tag = frame + 12 + plen;
-            if (decrypt) {
-                fr.in = frame + 12;
-                fr.out = jb.out + f * jb.frame_size;
-            } else {
+            if (win) {
                 fr.in = jb.in + f * jb.frame_size;
-                fr.out = frame + 12;
+                fr.pos = pos0 + f * fl;
+            } else {
+                uint8_t* frame = const_cast<uint8_t*>(decrypt ? jb.in : jb.out) + f * fl;
+                fr.hdr = frame;
+                fr.tag = frame + 12 + plen;
+                if (decrypt) {
+                    fr.in = frame + 12;
+                    fr.out = jb.out + f * jb.frame_size;
+                } else {
+                    fr.in = jb.in + f * jb.frame_size;
+                    fr.out = frame + 12;
+                }
             }
             fr.aad = jb.aad_len ? jb.aad + f * jb.aad_len : nullptr;
             fr.aad_len = jb.aad_len;
@@ -206,21 +235,29 @@ int run_frames(Device& d, Slot& slot, hipStream_t s, const std::vector<Job>& job
     if (frames.empty()) return MXEC_OK;
     const uint32_t* te = nullptr;
     MXEC_TRY(te_tables(d, &te));
-    DescWriter w(slot);
+    DescWriter w(slot, arena);
     const size_t o_keys = w.add(keys.size() * sizeof(GcmKey));
     const size_t o_fr = w.add(frames.size() * sizeof(GcmFrame));
     std::memcpy(w.data() + o_keys, keys.data(), keys.size() * sizeof(GcmKey));
     std::memcpy(w.data() + o_fr, frames.data(), frames.size() * sizeof(GcmFrame));
     char* dev = nullptr;
     MXEC_TRY(w.commit(s, &dev));
-    MXEC_TRY(affinity_check(d, &slot, s, "gcm frames"));
-    GcmArgs a{};
+    MXEC_TRY(affinity_check(d, &slot, s, "gcm frames", arena));
+    GcmWinArgs a{};
     a.te = te;
-    a.keys = reinterpret_cast<const GcmKey*>(dev + o_keys);
+    a.keys = keys_dev ? keys_dev : reinterpret_cast<const GcmKey*>(dev + o_keys);
     a.frames = reinterpret_cast<const GcmFrame*>(dev + o_fr);
     a.status = status_dev;
     a.n_frames = frames.size();
-    MXEC_HIP(launch_gcm_frames(a, decrypt, d.n_cus, s));
+    if (win) {
+        a.base = win->w.base_dev;
+        a.chunk_size = win->w.chunk_size;
+        a.slot_stride = win->w.slot_stride;
+        a.slots = win->w.slots;
+        MXEC_HIP(launch_gcm_frames_window(a, d.n_cus, s));
+    } else {
+        MXEC_HIP(launch_gcm_frames(a, decrypt, d.n_cus, s));
+    }
     return w.finish(s);
 }
 
@@ -253,6 +290,38 @@ int frame_error(const int32_t* st, uint64_t nf, uint64_t first_index, const uint
 }
 
 }  // namespace
+
+// The argument checks of the window form (include/maxio_ec.h
+// mxec_frames_encrypt_window_device), all before anything is queued.
+int mxec::gcm_window_check(const mxec_frames_job& q, const mxec_frames_window& w, bool need_key) {
+    if ((need_key && !q.key) || (q.len && !q.in_dev) || (q.aad_len && !q.aad_dev) || !w.base_dev)
+        return set_error(MXEC_E_INVALID_ARG, "null argument");
+    MXEC_TRY(check_frame_size(q.frame_size));
+    // The kernel's offsets within a frame are 32-bit.
+    if (q.frame_size > 0x7FFFFF00u) return set_error(MXEC_E_INVALID_ARG, "frame_size must be below 2^31 for a window");
+    if (w.chunk_size == 0) return set_error(MXEC_E_INVALID_ARG, "chunk_size must be > 0");
+    if (w.slot_stride < w.chunk_size) return set_error(MXEC_E_INVALID_ARG, "slot_stride must be >= chunk_size");
+    if (w.slots == 0) return set_error(MXEC_E_INVALID_ARG, "slots must be >= 1");
+    if (w.slots > (uint64_t(1) << 62) / w.chunk_size)
+        return set_error(MXEC_E_INVALID_ARG, "a window of 2^62 bytes or more");
+    const uint64_t nf = n_frames(q.len, q.frame_size);
+    if (q.len > UINT64_MAX - MXEC_FRAME_OVERHEAD * nf) return set_error(MXEC_E_INVALID_ARG, "frame stream length overflows");
+    const uint64_t span = q.len + MXEC_FRAME_OVERHEAD * nf;
+    if (span > w.slots * w.chunk_size)
+        return set_error(MXEC_E_INVALID_ARG, "the job's " + std::to_string(span) + " stream bytes exceed the window's " +
+                                                 std::to_string(w.slots * w.chunk_size) + ": it would overwrite itself");
+    return MXEC_OK;
+}
+
+// The window form's launch (checked by gcm_window_check); key_dev: the job's
+// GcmKey resident in HBM, or null to prepare it from q.key for this launch.
+int mxec::gcm_encrypt_window(Device& d, Slot& slot, hipStream_t s, const GcmKey* key_dev, const mxec_frames_job& q,
+                             uint64_t stream_off, const mxec_frames_window& w, DescArena* arena) {
+    const Job jb{q.key, prefix_word(q.nonce_prefix), q.frame_size, q.first_index, q.aad_dev, q.aad_len, q.in_dev, q.len,
+                 nullptr};
+    const Window win{w, stream_off};
+    return run_frames(d, slot, s, {jb}, false, nullptr, key_dev, &win, arena);
+}
 
 extern "C" {
 
@@ -346,6 +415,19 @@ int mxec_frames_encrypt_device(mxec_ctx* ctx, int dev, void* stream, const mxec_
         DevScope ds;
         MXEC_TRY(ds.open(ctx, dev));
         return run_frames(*ds.d, *ds.slot, static_cast<hipStream_t>(stream), js, false, nullptr);
+    });
+}
+
+int mxec_frames_encrypt_window_device(mxec_ctx* ctx, int dev, void* stream, const mxec_frames_job* job,
+                                      uint64_t stream_off, const void* win_) {
+    return guarded([&] {
+        const auto* win = static_cast<const mxec_frames_window*>(win_);
+        if (!job || !win) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        MXEC_TRY(gcm_window_check(*job, *win, true));
+        if (job->len == 0) return MXEC_OK;
+        DevScope ds;
+        MXEC_TRY(ds.open(ctx, dev));
+        return gcm_encrypt_window(*ds.d, *ds.slot, static_cast<hipStream_t>(stream), nullptr, *job, stream_off, *win);
     });
 }
 

@@ -219,6 +219,71 @@ __device__ __forceinline__ void store16_be(uint8_t* p, u32x4 v) {
     *reinterpret_cast<u32x4a1*>(p) = u32x4a1{bswap(v.x), bswap(v.y), bswap(v.z), bswap(v.w)};
 }
 
+// ---- the windowed destination (encrypt into a ring of chunk slots) ------------
+// One frame's view of the ring, uniform over its 256 lanes (kept in SGPRs).
+// The frame's first chunk c0 holds its first d0 bytes from p0 on; its chunk
+// c0 + t (t >= 1) starts at pa + t * stride while t < wrap and at
+// pb + t * stride once the ring has wrapped to slot 0.  Frame offsets are
+// 32-bit (a frame is shorter than 2^31 bytes); only the stride multiply and
+// the final add are 64-bit.
+struct WinFrame {
+    uintptr_t p0, pa, pb;
+    uint64_t stride;
+    uint32_t d0;    // frame bytes in front of the first chunk boundary (>= 1)
+    uint32_t cs;    // chunk_size; 2^32 - 1 when larger (no second boundary can then fall in a frame)
+    uint32_t wrap;  // chunks from c0 to the one in slot 0 (clamped like cs)
+};
+struct WinCursor {
+    uint8_t* p;
+    uint32_t room;  // bytes from p to its chunk's end
+    uint32_t t;
+};
+__device__ __forceinline__ uint32_t uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ uint64_t uniform(uint64_t x) {
+    return uint64_t(uniform(uint32_t(x))) | uint64_t(uniform(uint32_t(x >> 32))) << 32;
+}
+__device__ __forceinline__ uint8_t* win_chunk(const WinFrame& w, uint32_t t) {
+    return reinterpret_cast<uint8_t*>((t < w.wrap ? w.pa : w.pb) + uint64_t(t) * w.stride);
+}
+// Where frame byte o lives.
+__device__ __forceinline__ WinCursor win_seek(const WinFrame& w, uint32_t o) {
+    WinCursor c;
+    if (o < w.d0) {
+        c.p = reinterpret_cast<uint8_t*>(w.p0 + o);
+        c.room = w.d0 - o;
+        c.t = 0;
+    } else {
+        const uint32_t x = o - w.d0, q = x / w.cs, rem = x - q * w.cs;
+        c.t = q + 1;
+        c.p = win_chunk(w, c.t) + rem;
+        c.room = w.cs - rem;
+    }
+    return c;
+}
+// The first n (<= 16) bytes of v (big-endian words) from c on, one by one,
+// stepping to the next chunk's slot at every boundary.
+__device__ __forceinline__ void win_store_bytes(const WinFrame& w, WinCursor c, u32x4 v, uint32_t n) {
+#pragma unroll 1
+    for (uint32_t i = 0; i < n; ++i) {
+        if (c.room == 0) {
+            c.p = win_chunk(w, ++c.t);
+            c.room = w.cs;
+        }
+        *c.p++ = uint8_t(v.x >> 24);
+        v.x = __builtin_amdgcn_alignbit(v.x, v.y, 24);
+        v.y = __builtin_amdgcn_alignbit(v.y, v.z, 24);
+        v.z = __builtin_amdgcn_alignbit(v.z, v.w, 24);
+        v.w <<= 8;
+        --c.room;
+    }
+}
+// n bytes of v at frame offset o: one store when no boundary cuts them.
+__device__ __forceinline__ void win_store(const WinFrame& w, uint32_t o, const u32x4& v, uint32_t n) {
+    const WinCursor c = win_seek(w, o);
+    if (n == 16 && c.room >= 16) store16_be(c.p, v);
+    else win_store_bytes(w, c, v, n);
+}
+
 // LDS: the four T-tables replicated 32 times, laid out so that a lookup's
 // address is ONE v_perm_b32 of the state word and a per-lane constant:
 //     byte offset = pair * 65536 + x * 256 + t * 128 + (lane % 32) * 4
@@ -247,8 +312,14 @@ static_assert(kGcmLdsBytes <= 160 * 1024, "GCM LDS image exceeds 160 KiB");
 
 typedef const uint32_t __attribute__((address_space(3)))* lds_u32p;
 
-template <bool kDecrypt>
-__global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(GcmArgs a) {
+// kWindow (encrypt only): the frames go to a ring of chunk slots (GcmWinArgs)
+// instead of to one contiguous run.  A frame that no chunk boundary cuts gets
+// its pointers once and runs the contiguous form's stores; a cut frame sends
+// every store through win_store.  Which it is, is uniform and held in an SGPR.
+template <bool kDecrypt, bool kWindow = false>
+__global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
+    typename std::conditional<kWindow, GcmWinArgs, GcmArgs>::type a) {
+    static_assert(!(kDecrypt && kWindow), "the window form encrypts");
     extern __shared__ uint32_t smem[];
     uint32_t* te = smem;
     // The lookup addresses assume the tables start at LDS address 0.
@@ -286,6 +357,36 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(GcmArgs a)
         __syncthreads();
         const uint32_t* rk = key->rk;
         const uint32_t nb = (fr.len + 15) / 16, na = (fr.aad_len + 15) / 16;
+        // Where the frame goes.
+        uint8_t *hdr_p = fr.hdr, *out_p = fr.out, *tag_p = fr.tag;
+        bool cut = false;
+        WinFrame wf{};
+        if constexpr (kWindow) {
+            const uint64_t cs = a.chunk_size, slots = a.slots, stride = a.slot_stride;
+            const uint64_t c0 = fr.pos / cs, r0 = fr.pos - c0 * cs;  // the frame's one 64-bit division
+            const uint64_t s0 = c0 >= slots ? c0 - slots : c0;      // pos < 2 * slots * chunk_size
+            const uint64_t room = cs - r0, wrap = slots - s0;
+            wf.pa = uniform(uint64_t(reinterpret_cast<uintptr_t>(a.base)) + s0 * stride);
+            wf.pb = uniform(uint64_t(reinterpret_cast<uintptr_t>(a.base)) - wrap * stride);
+            wf.p0 = uniform(uint64_t(wf.pa) + r0);
+            wf.stride = stride;
+            wf.d0 = uniform(uint32_t(min(room, uint64_t(0xFFFFFFFFu))));
+            wf.cs = uint32_t(min(cs, uint64_t(0xFFFFFFFFu)));
+            wf.wrap = uniform(uint32_t(min(wrap, uint64_t(0xFFFFFFFFu))));
+            cut = uniform(uint32_t(live && room < uint64_t(fr.len) + 28u)) != 0;
+            hdr_p = reinterpret_cast<uint8_t*>(wf.p0);
+            out_p = hdr_p + 12;
+            tag_p = out_p + fr.len;
+        }
+        // 16 bytes, or the partial last block's n, of the payload at offset off.
+        auto put16 = [&](uint32_t off, const u32x4& v) {
+            if (kWindow && cut) win_store(wf, 12 + off, v, 16);
+            else store16_be(out_p + off, v);
+        };
+        auto putn = [&](uint32_t off, const u32x4& v, uint32_t n) {
+            if (kWindow && cut) win_store(wf, 12 + off, v, n);
+            else store_partial_be(out_p + off, v, n);
+        };
         const uint32_t m = live ? na + nb + 1 : 0;
         // The 12-byte nonce: prefix || index (u64 LE).  Encrypt builds it and
         // writes the frame header; decrypt reads the stored one (crypto.rs:323).
@@ -320,9 +421,9 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(GcmArgs a)
                 u32x4 in = n == 16 ? load16_be(fr.in + off) : load_partial_be(fr.in + off, n);
                 u32x4 out = {in.x ^ ks.x, in.y ^ ks.y, in.z ^ ks.z, in.w ^ ks.w};
                 if (n == 16) {
-                    store16_be(fr.out + off, out);
+                    put16(off, out);
                 } else {
-                    store_partial_be(fr.out + off, out, n);
+                    putn(off, out, n);
                     // keystream bytes past n must not enter GHASH
                     out.x &= mask_be(n, 0); out.y &= mask_be(n, 1);
                     out.z &= mask_be(n, 2); out.w &= mask_be(n, 3);
@@ -368,8 +469,8 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(GcmArgs a)
 #endif
             const u32x4 o0 = {in0.x ^ a0, in0.y ^ a1, in0.z ^ a2, in0.w ^ a3};
             const u32x4 o1 = {in1.x ^ b0, in1.y ^ b1, in1.z ^ b2, in1.w ^ b3};
-            store16_be(fr.out + 16 * j0, o0);
-            store16_be(fr.out + 16 * j1, o1);
+            put16(16 * j0, o0);
+            put16(16 * j1, o1);
             fold(kDecrypt ? in0 : o0);
             fold(kDecrypt ? in1 : o1);
             last = i + 256;
@@ -407,15 +508,24 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(GcmArgs a)
                 const u32x4 want = load_partial_be(fr.tag, 16);
                 const bool ok = want.x == tag.x && want.y == tag.y && want.z == tag.z && want.w == tag.w;
                 a.status[f] = stored != fr.index ? 2 : ok ? 0 : 1;
+            } else if (kWindow && cut) {  // a boundary may fall inside either
+                win_store_bytes(wf, win_seek(wf, 0), u32x4{n0, n1, n2, 0u}, 12);
+                win_store_bytes(wf, win_seek(wf, 12 + fr.len), tag, 16);
             } else {
-                store_partial_be(fr.hdr, u32x4{n0, n1, n2, 0u}, 12);
-                store_partial_be(fr.tag, tag, 16);
+                store_partial_be(hdr_p, u32x4{n0, n1, n2, 0u}, 12);
+                store_partial_be(tag_p, tag, 16);
             }
         }
     }
 }
 
 }  // namespace
+
+// One workgroup per kGcmGroups frames, at most one per CU (grid-stride).
+static uint32_t gcm_grid(uint64_t n_frames, int n_cus) {
+    const uint64_t groups = (n_frames + kGcmGroups - 1) / kGcmGroups;
+    return uint32_t(std::min<uint64_t>(groups, uint64_t(n_cus)));
+}
 
 hipError_t launch_gcm_frames(const GcmArgs& a, bool decrypt, int n_cus, hipStream_t s) {
     if (a.n_frames == 0) return hipSuccess;
@@ -430,12 +540,22 @@ hipError_t launch_gcm_frames(const GcmArgs& a, bool decrypt, int n_cus, hipStrea
         return e;
     }();
     if (attr != hipSuccess) return attr;
-    const uint64_t groups = (a.n_frames + kGcmGroups - 1) / kGcmGroups;
-    const uint64_t grid = std::min<uint64_t>(groups, uint64_t(n_cus));
+    const uint64_t grid = gcm_grid(a.n_frames, n_cus);
     if (decrypt)
         hipLaunchKernelGGL(gcm_frames_kernel<true>, dim3(uint32_t(grid)), dim3(256 * kGcmGroups), kGcmLdsBytes, s, a);
     else
         hipLaunchKernelGGL(gcm_frames_kernel<false>, dim3(uint32_t(grid)), dim3(256 * kGcmGroups), kGcmLdsBytes, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_gcm_frames_window(const GcmWinArgs& a, int n_cus, hipStream_t s) {
+    if (a.n_frames == 0) return hipSuccess;
+    static const hipError_t attr =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gcm_frames_kernel<false, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, int(kGcmLdsBytes));
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL((gcm_frames_kernel<false, true>), dim3(gcm_grid(a.n_frames, n_cus)), dim3(256 * kGcmGroups),
+                       kGcmLdsBytes, s, a);
     return hipGetLastError();
 }
 

@@ -198,6 +198,20 @@ int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const 
                   const std::vector<uint64_t>& lens, uint32_t which, uint8_t* out_dev, uint64_t stride,
                   const SumsUpdate* upd = nullptr, DescArena* arena = nullptr);
 
+// AES-256-GCM frames (gcm.cpp).  gcm_prepare_key fills a data key's tables
+// (kernels.hpp GcmKey: key schedule, H^1..H^256, the position table of H^256;
+// ~30 us of host work): the frame entry points do it per call, a caller with
+// many launches under one key does it once and keeps the record in HBM.
+// gcm_encrypt_window: the launch of mxec_frames_encrypt_window_device over
+// arguments gcm_window_check has passed, enqueue-only; key_dev = that
+// resident record (q.key is then not read), or null to prepare q.key here;
+// arena = where the launch's tables go instead of the slot's ring.
+struct GcmKey;
+void gcm_prepare_key(const uint8_t key[32], GcmKey& out);
+int gcm_window_check(const mxec_frames_job& q, const mxec_frames_window& w, bool need_key);
+int gcm_encrypt_window(Device& d, Slot& slot, hipStream_t s, const GcmKey* key_dev, const mxec_frames_job& q,
+                       uint64_t stream_off, const mxec_frames_window& w, DescArena* arena = nullptr);
+
 // Creates the device's host-pipeline hub and its streams (pipe_hub.cpp),
 // called by mxec_open for every device.
 int pipe_open(Device& dev);

@@ -749,4 +749,16 @@ Slot& lock_slot(Device& dev, std::unique_lock<std::mutex>& lk) {
     return s;
 }
 
+void slots_settle(Device& dev) {
+    for (auto& sp : dev.slots) {
+        std::lock_guard<std::mutex> g(sp->mu);
+        for (DescBuf& b : sp->ring) {
+            if (!b.pending) continue;
+            (void)hipEventSynchronize(b.done);
+            b.pending = false;
+        }
+    }
+    (void)hipGetLastError();
+}
+
 }  // namespace mxec

@@ -465,5 +465,11 @@ struct mxec_ctx {
 
 namespace mxec {
 Slot& lock_slot(Device& dev, std::unique_lock<std::mutex>& lk);
+// Before a caller destroys a stream of its own that launches of this device
+// ran on: every slot's descriptor-ring entry still fenced by an event is
+// waited for and released, so that no entry keeps an event whose last record
+// was on that stream (the runtime looks at an event's last stream when it
+// synchronises on it, destroyed or not).  The caller has drained the stream.
+void slots_settle(Device& dev);
 
 }  // namespace mxec

@@ -22,13 +22,30 @@
 // its last byte's upload (run_body_sums' update form; the chains' state stays
 // in HBM between runs, so nothing waits between them).  A slot's reuse then
 // also waits for its chunk's last run.
+//
+// The encrypted writer (mxec_writer_open_encrypted; put_object_chunked_encrypted
+// filesystem.rs:835-1060, frames of crypto.rs:94-117): the caller writes
+// plaintext, which goes up into a ring of kRingRuns stretches of 1 MiB, not
+// into the window.  With a stretch's last byte (or the body's) one launch of
+// the GCM kernel's window form encrypts its 16 frames straight into the chunk
+// slots (frame_plan.hpp has the arithmetic), on the main stream behind the
+// upload, under key tables prepared once at open; its AADs are hashed on the
+// host and go up in front of it.  The ciphertext comes down on a stream of its
+// own through two more staging pieces and goes to the chunk files one or two
+// pieces later; a chunk the launch completes takes complete() as ever.  The
+// body digests run over the plaintext ring, one run per stretch.  A stretch is
+// reused once its launch and its digest run have finished, a slot once its
+// chunk's hash, fold and download have.
 #include <fcntl.h>
 #include <unistd.h>
 
 #include <cerrno>
 #include <cstring>
 
+#include "frame_plan.hpp"
+#include "kernels.hpp"
 #include "ops.hpp"
+#include "sha256_host.hpp"
 #include "shard_files.hpp"
 #include "writer_plan.hpp"
 
@@ -54,6 +71,45 @@ struct WindowSlot {
 // Table bytes one digest run takes (pointers, CRC tile map and scratch of at
 // most kSumRun bytes; the arena chains a block should one take more).
 constexpr size_t kSumRunTables = 512;
+
+constexpr int kRingRuns = 4;    // plaintext stretches (kEncRun each) resident in HBM
+constexpr int kDownPieces = 2;  // page-locked pieces for ciphertext on its way down
+
+struct RingRun {
+    hipEvent_t encrypted = nullptr;  // the stretch's encrypt launch finished
+    hipEvent_t summed = nullptr;     // ... and its digest run (with body digests)
+    bool busy = false, sum_busy = false;
+    DescArena sum_tables, enc_tables;  // the launches' tables: free again with the events above
+};
+// A stretch of the frame stream, at most kPiece, between its slots and the chunk files.
+struct DownPiece {
+    PinnedBuf buf;
+    hipEvent_t landed = nullptr;
+    uint64_t off = 0, len = 0;
+};
+struct EncState {
+    uint64_t plain_len = 0;
+    WriterPlan pplan;  // the plaintext as one body: the over-run and short-finish texts are in its bytes
+    uint8_t key[32];
+    uint8_t prefix[4];
+    GcmKey tables;     // the host copy of what key_dev holds
+    DevBuf key_dev;
+    std::vector<uint8_t> aad_msg;  // aad_prefix, then room for the index
+    DevBuf ring, aad_dev;          // kRingRuns * kEncRun | kRingRuns * kEncFrames * 32
+    PinnedBuf aad_host;
+    RingRun runs[kRingRuns];
+    hipStream_t down_s = nullptr;
+    DownPiece down[kDownPieces];
+    uint64_t down_head = 0, down_next = 0;  // pieces gone to their files | queued
+    uint64_t filed = 0;                     // stream bytes in the chunk files
+
+    uint8_t* ring_ptr(uint64_t run) const { return static_cast<uint8_t*>(ring.p) + (run % kRingRuns) * kEncRun; }
+    size_t aad_at(uint64_t run) const { return size_t(run % kRingRuns) * kEncFrames * 32; }
+    ~EncState() {  // neither key outlives the writer on the host
+        explicit_bzero(key, sizeof key);
+        explicit_bzero(&tables, sizeof tables);
+    }
+};
 
 }  // namespace
 
@@ -94,6 +150,8 @@ struct mxec_writer {
     mxec_body_sums sums{};          // after finish()
     uint8_t* sums_out_dev() const { return static_cast<uint8_t*>(sum_state.p) + MXEC_SUMS_STATE_BYTES; }
 
+    std::unique_ptr<EncState> enc;  // mxec_writer_open_encrypted; null otherwise
+
     uint8_t* slot_ptr(uint64_t slot) const { return static_cast<uint8_t*>(window.p) + slot * sa; }
     uint8_t* parity_set(int which) const { return static_cast<uint8_t*>(parity.p) + uint64_t(which) * m * sa; }
 
@@ -103,12 +161,33 @@ struct mxec_writer {
         (void)hipSetDevice(dev->id);
         // Nothing of ours may still run when the buffers go.
         if (s) (void)hipStreamSynchronize(s);
+        if (sum_s) (void)hipStreamSynchronize(sum_s);
+        if (enc && enc->down_s) (void)hipStreamSynchronize(enc->down_s);
+        for (WindowSlot& w : slots)
+            if (w.hash) (void)hipStreamSynchronize(w.hash);
+        // The parity passes and chunk hashes took their tables from the slots'
+        // rings, fenced by events on the streams destroyed below.
+        slots_settle(*dev);
         if (sum_s) {
             (void)hipStreamSynchronize(sum_s);
             affinity_untag(sum_s);
             (void)hipStreamDestroy(sum_s);
         }
         if (sums_done) (void)hipEventDestroy(sums_done);
+        if (enc) {
+            if (enc->down_s) {
+                (void)hipStreamSynchronize(enc->down_s);
+                affinity_untag(enc->down_s);
+                (void)hipStreamDestroy(enc->down_s);
+            }
+            for (RingRun& r : enc->runs) {
+                if (r.encrypted) (void)hipEventDestroy(r.encrypted);
+                if (r.summed) (void)hipEventDestroy(r.summed);
+            }
+            for (DownPiece& p : enc->down)
+                if (p.landed) (void)hipEventDestroy(p.landed);
+            if (enc->key_dev.p) (void)hipMemset(enc->key_dev.p, 0, sizeof(GcmKey));
+        }
         for (WindowSlot& w : slots) {
             if (w.summed) (void)hipEventDestroy(w.summed);
             if (w.hash) {
@@ -158,7 +237,7 @@ int collect(mxec_writer& w, uint64_t slot) {
     if (ws.chunk == UINT64_MAX) return MXEC_OK;
     MXEC_HIP(hipEventSynchronize(ws.hashed));
     if (w.m) MXEC_HIP(hipEventSynchronize(ws.folded));
-    if (w.which) MXEC_HIP(hipEventSynchronize(ws.summed));  // queued before the chunk completed
+    if (w.which && !w.enc) MXEC_HIP(hipEventSynchronize(ws.summed));  // queued before the chunk completed
     w.sha[ws.chunk] = hex(static_cast<const uint8_t*>(w.hdig.p) + ws.dig_at * 32, 32);
     ws.chunk = UINT64_MAX;
     return MXEC_OK;
@@ -301,13 +380,160 @@ int write_parity_file(mxec_writer& w, uint32_t i) {
     return close_chunk_file(w, j);
 }
 
+// ---- the encrypted writer ---------------------------------------------------------------------------
+
+// The oldest piece on its way down, to its chunks' files.
+int file_piece(mxec_writer& w) {
+    EncState& e = *w.enc;
+    DownPiece& p = e.down[e.down_head % kDownPieces];
+    MXEC_HIP(hipEventSynchronize(p.landed));
+    const uint8_t* bytes = static_cast<const uint8_t*>(p.buf.p);
+    MXEC_TRY(writer_cut(w.plan, p.off, p.len, [&](const WriterRun& c) -> int {
+        if (c.opens) MXEC_TRY(open_chunk_file(w, c.chunk));
+        MXEC_TRY(write_chunk_bytes(w, c.chunk, bytes + c.src, c.len));
+        return c.completes ? close_chunk_file(w, c.chunk) : MXEC_OK;
+    }));
+    e.filed = p.off + p.len;
+    ++e.down_head;
+    return MXEC_OK;
+}
+// Every queued piece that holds stream bytes below `upto`, to the files.
+int file_until(mxec_writer& w, uint64_t upto) {
+    while (w.enc->filed < upto && w.enc->down_head < w.enc->down_next) MXEC_TRY(file_piece(w));
+    return MXEC_OK;
+}
+
+// Stream bytes [off, off + len), len <= kPiece, from their slots to a staging
+// piece, behind whatever the download stream already waits for.
+int fetch_piece(mxec_writer& w, uint64_t off, uint64_t len) {
+    EncState& e = *w.enc;
+    if (e.down_next - e.down_head == kDownPieces) MXEC_TRY(file_piece(w));
+    DownPiece& p = e.down[e.down_next % kDownPieces];
+    uint8_t* dst = static_cast<uint8_t*>(p.buf.p);
+    MXEC_TRY(ring_segments(w.plan.chunk_size, w.plan.slots, off, len, [&](uint64_t slot, uint64_t at, uint64_t src, uint64_t n) -> int {
+        MXEC_HIP(hipMemcpyAsync(dst + src, w.slot_ptr(slot) + at, size_t(n), hipMemcpyDeviceToHost, e.down_s));
+        return MXEC_OK;
+    }));
+    MXEC_HIP(hipEventRecord(p.landed, e.down_s));
+    p.off = off;
+    p.len = len;
+    ++e.down_next;
+    return MXEC_OK;
+}
+
+// The stretch's digest run over the plaintext ring, behind its upload on w.s.
+int queue_plain_sums(mxec_writer& w, const EncRun& q) {
+    EncState& e = *w.enc;
+    RingRun& rr = e.runs[q.index % kRingRuns];
+    MXEC_TRY(rr.sum_tables.reserve(std::max<size_t>(4096, kSumRunTables)));
+    MXEC_HIP(hipEventRecord(w.uploaded, w.s));
+    MXEC_HIP(hipStreamWaitEvent(w.sum_s, w.uploaded, 0));
+    {
+        DevScope ds;
+        MXEC_TRY(ds.open(w.ctx, w.dev_index));
+        const SumsUpdate upd{static_cast<uint8_t*>(w.sum_state.p),
+                             (q.index == 0 ? MXEC_SUMS_F_FIRST : 0u) | (q.last ? MXEC_SUMS_F_FINAL : 0u)};
+        MXEC_TRY(run_body_sums(*ds.d, *ds.slot, w.sum_s, {e.ring_ptr(q.index)}, {q.plain_len}, w.which, w.sums_out_dev(),
+                               sizeof(mxec_body_sums), &upd, &rr.sum_tables));
+    }
+    MXEC_HIP(hipEventRecord(rr.summed, w.sum_s));
+    rr.sum_busy = true;
+    if (!q.last) return MXEC_OK;
+    MXEC_HIP(hipMemcpyAsync(w.hsums.p, w.sums_out_dev(), sizeof(mxec_body_sums), hipMemcpyDeviceToHost, w.sum_s));
+    MXEC_HIP(hipEventRecord(w.sums_done, w.sum_s));
+    return MXEC_OK;
+}
+
+// The stretch's plaintext is whole in the ring (its uploads queued on w.s):
+// its frames into the window, its ciphertext on its way down, its chunks
+// completed.
+int queue_enc_run(mxec_writer& w, const EncRun& q) {
+    EncState& e = *w.enc;
+    RingRun& rr = e.runs[q.index % kRingRuns];
+    const WriterPlan& p = w.plan;
+    // Back-pressure: a slot the launch opens must be done with its last chunk
+    // (hash and fold: collect; download: in its file).  The launch touches at
+    // most p.slots chunks, so that chunk was completed by an earlier launch.
+    MXEC_TRY(writer_cut(p, q.stream_off, q.stream_len, [&](const WriterRun& c) -> int {
+        if (!c.opens || !p.reuses(c.chunk)) return MXEC_OK;
+        MXEC_TRY(file_until(w, (p.evicts(c.chunk) + 1) * p.chunk_size));
+        return collect(w, p.slot_of(c.chunk));
+    }));
+    if (w.which) MXEC_TRY(queue_plain_sums(w, q));
+    // Frame i's AAD = SHA-256(aad_prefix || i as u64 LE) (build_frame_aad, filesystem.rs:118-128).
+    uint8_t* ah = static_cast<uint8_t*>(e.aad_host.p) + e.aad_at(q.index);
+    uint8_t* ad = static_cast<uint8_t*>(e.aad_dev.p) + e.aad_at(q.index);
+    const size_t pl = e.aad_msg.size() - 8;
+    for (uint64_t f = 0; f < q.frames; ++f) {
+        for (int b = 0; b < 8; ++b) e.aad_msg[pl + size_t(b)] = uint8_t((q.first_frame + f) >> (8 * b));
+        sha256_host(e.aad_msg.data(), e.aad_msg.size(), ah + f * 32);
+    }
+    MXEC_HIP(hipMemcpyAsync(ad, ah, size_t(q.frames) * 32, hipMemcpyHostToDevice, w.s));
+    mxec_frames_job job{};
+    std::memcpy(job.nonce_prefix, e.prefix, 4);
+    job.frame_size = uint32_t(kFramePlain);
+    job.first_index = q.first_frame;
+    job.aad_dev = ad;
+    job.aad_len = 32;
+    job.in_dev = e.ring_ptr(q.index);
+    job.len = q.plain_len;
+    const mxec_frames_window win{static_cast<uint8_t*>(w.window.p), p.chunk_size, w.sa, p.slots};
+    {
+        DevScope ds;
+        MXEC_TRY(ds.open(w.ctx, w.dev_index));
+        MXEC_TRY(gcm_window_check(job, win, false));
+        MXEC_TRY(rr.enc_tables.reserve(4096));
+        MXEC_TRY(gcm_encrypt_window(*ds.d, *ds.slot, w.s, static_cast<const GcmKey*>(e.key_dev.p), job, q.stream_off, win,
+                                    &rr.enc_tables));
+    }
+    MXEC_HIP(hipEventRecord(rr.encrypted, w.s));
+    rr.busy = true;
+    MXEC_HIP(hipStreamWaitEvent(e.down_s, rr.encrypted, 0));
+    for (uint64_t off = 0; off < q.stream_len; off += kPiece)
+        MXEC_TRY(fetch_piece(w, q.stream_off + off, std::min(kPiece, q.stream_len - off)));
+    return writer_cut(p, q.stream_off, q.stream_len,
+                      [&](const WriterRun& c) -> int { return c.completes ? complete(w, c.chunk) : MXEC_OK; });
+}
+
+// `len` plaintext bytes (no over-run) into the ring, stretch by stretch.
+int enc_write(mxec_writer& w, const uint8_t* buf, uint64_t len) {
+    EncState& e = *w.enc;
+    for (uint64_t src = 0; src < len;) {
+        const uint64_t run = w.written / kEncRun, at = w.written - run * kEncRun;
+        const uint64_t n = std::min(len - src, kEncRun - at);
+        RingRun& rr = e.runs[run % kRingRuns];
+        if (at == 0) {  // the stretch's last tenant: the only wait for the ring
+            if (rr.busy) MXEC_HIP(hipEventSynchronize(rr.encrypted));
+            if (rr.sum_busy) MXEC_HIP(hipEventSynchronize(rr.summed));
+            rr.busy = rr.sum_busy = false;
+        }
+        MXEC_TRY(upload(w, e.ring_ptr(run) + at, buf + src, n));
+        const uint64_t from = w.written;
+        w.written += n;
+        src += n;
+        MXEC_TRY(enc_runs_due(e.plain_len, from, w.written, [&](const EncRun& q) { return queue_enc_run(w, q); }));
+    }
+    return MXEC_OK;
+}
+
 int finish(mxec_writer& w) {
-    if (w.written != w.plan.total_len) return set_error(MXEC_E_INVALID_ARG, writer_short_msg(w.plan, w.written));
+    if (w.enc) {
+        if (w.written != w.enc->plain_len)
+            return set_error(MXEC_E_INVALID_ARG, writer_short_msg(w.enc->pplan, w.written));
+        MXEC_TRY(file_until(w, w.plan.total_len));  // the last launch went with the last byte
+    } else if (w.written != w.plan.total_len) {
+        return set_error(MXEC_E_INVALID_ARG, writer_short_msg(w.plan, w.written));
+    }
     if (w.plan.total_len == 0) {  // one empty chunk (:740-743), no parity (:748)
         MXEC_TRY(open_chunk_file(w, 0));
         MXEC_TRY(close_chunk_file(w, 0));
-        if (w.which)  // one empty run, first and last
+        if (w.which && w.enc) {  // one empty run, first and last
+            EncRun q{};
+            q.last = true;
+            MXEC_TRY(queue_plain_sums(w, q));
+        } else if (w.which) {
             MXEC_TRY(writer_sum_due(w.plan, 0, 0, 0, [&](const SumRun& q) { return queue_sum_run(w, q); }));
+        }
         MXEC_TRY(complete(w, 0));
     }
     const uint64_t k = w.plan.k;
@@ -337,13 +563,70 @@ int finish(mxec_writer& w) {
     return write_file(w.dir / "manifest.json", reinterpret_cast<const uint8_t*>(js.data()), js.size());
 }
 
+// What mxec_writer_open_encrypted adds to an open.
+struct EncOpen {
+    uint64_t plain_len;
+    const uint8_t* key;
+    const uint8_t* prefix;
+    const uint8_t* aad_prefix;
+    uint32_t aad_prefix_len;
+};
+
+// The encrypted writer's own buffers, streams and key tables.
+int open_enc(mxec_writer& w, const EncOpen& eo) {
+    w.enc = std::make_unique<EncState>();
+    EncState& e = *w.enc;
+    e.plain_len = eo.plain_len;
+    e.pplan = WriterPlan::make(kEncRun, eo.plain_len, 0);
+    std::memcpy(e.key, eo.key, 32);
+    std::memcpy(e.prefix, eo.prefix, 4);
+    e.aad_msg.assign(size_t(eo.aad_prefix_len) + 8, 0);
+    if (eo.aad_prefix_len) std::memcpy(e.aad_msg.data(), eo.aad_prefix, eo.aad_prefix_len);
+    // The key schedule, H^1..H^256 and the position table, once for every launch.
+    gcm_prepare_key(e.key, e.tables);
+    MXEC_TRY(e.key_dev.ensure(sizeof(GcmKey)));
+    MXEC_HIP(hipMemcpy(e.key_dev.p, &e.tables, sizeof(GcmKey), hipMemcpyHostToDevice));
+    const uint64_t runs = std::min<uint64_t>(kRingRuns, enc_run_count(eo.plain_len));
+    MXEC_TRY(e.ring.ensure(size_t(runs <= 1 ? std::max<uint64_t>(eo.plain_len, 256) : runs * kEncRun)));
+    MXEC_TRY(e.aad_dev.ensure(size_t(kRingRuns * kEncFrames * 32)));
+    MXEC_TRY(e.aad_host.ensure(size_t(kRingRuns * kEncFrames * 32)));
+    for (RingRun& r : e.runs) {
+        MXEC_TRY(new_event(&r.encrypted));
+        if (w.which) MXEC_TRY(new_event(&r.summed));
+        r.sum_tables.owner = r.enc_tables.owner = w.dev;
+    }
+    MXEC_TRY(new_stream(w, &e.down_s));
+    for (DownPiece& p : e.down) {
+        MXEC_TRY(p.buf.ensure(size_t(std::min(kPiece, std::max<uint64_t>(w.plan.total_len, 4096)))));
+        MXEC_TRY(new_event(&p.landed));
+    }
+    return MXEC_OK;
+}
+
 int open_writer(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uint32_t parity_shards, uint64_t total_len,
-                uint64_t plaintext_size, uint64_t window_bytes, uint32_t which, void** out) {
+                uint64_t plaintext_size, uint64_t window_bytes, uint32_t which, void** out,
+                const EncOpen* eo = nullptr) {
     return guarded([&]() -> int {
         if (!ctx || !ec_dir || !out) return set_error(MXEC_E_INVALID_ARG, "null argument");
         *out = nullptr;
+        if (eo && (!eo->key || !eo->prefix || (eo->aad_prefix_len && !eo->aad_prefix)))
+            return set_error(MXEC_E_INVALID_ARG, "null argument");
         if (chunk_size == 0) return set_error(MXEC_E_INVALID_ARG, "chunk_size must be > 0");
         if (which & ~uint32_t(0x1F)) return set_error(MXEC_E_INVALID_ARG, "unknown digest flag");
+        if (eo) {
+            // k, the chunk lengths and the guards below come from the frame stream's length.
+            if (!frame_stream_len(eo->plain_len, &total_len))
+                return set_error(MXEC_E_INVALID_ARG, "plaintext_len: the frame stream does not fit in 64 bits");
+            plaintext_size = eo->plain_len;
+            // One launch writes up to kEncRunStream bytes, which touch
+            // ceil(kEncRunStream / chunk_size) + 1 chunks at the most: the
+            // window holds at least those (two, for chunks of 1 MiB and more).
+            if (chunk_size < kEncRunStream) {
+                const uint64_t need = ((kEncRunStream - 1) / chunk_size + 2) * chunk_size;
+                const uint64_t asked = window_bytes ? window_bytes : WriterPlan::kDefaultSlots * chunk_size;
+                window_bytes = std::max(asked, need);
+            }
+        }
         auto w = std::make_unique<mxec_writer>();
         w->plan = WriterPlan::make(chunk_size, total_len, window_bytes);
         w->m = parity_shards > 0 && total_len > 0 ? parity_shards : 0;  // :748
@@ -370,7 +653,9 @@ int open_writer(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uint32_t
         MXEC_TRY(w->dig.ensure(size_t((n_slots + 1 + w->m) * 32)));
         MXEC_TRY(w->hdig.ensure(size_t((n_slots + 1 + w->m) * 32)));
         for (int b = 0; b < kPieces; ++b) {
-            MXEC_TRY(w->stage[b].ensure(size_t(std::min(kPiece, std::max<uint64_t>(chunk_size, 4096)))));
+            // A plain writer's uploads end with their chunk, an encrypted one's with their MiB of plaintext.
+            const uint64_t longest = eo ? std::max<uint64_t>(chunk_size, eo->plain_len) : chunk_size;
+            MXEC_TRY(w->stage[b].ensure(size_t(std::min(kPiece, std::max<uint64_t>(longest, 4096)))));
             MXEC_TRY(new_event(&w->staged[b]));
         }
         MXEC_TRY(new_stream(*w, &w->s, true));
@@ -388,12 +673,14 @@ int open_writer(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uint32_t
             MXEC_TRY(new_stream(*w, &w->sum_s));
             MXEC_TRY(new_event(&w->sums_done));
             for (WindowSlot& ws : w->slots) {
+                if (eo) continue;  // an encrypted writer's runs are over the plaintext ring (open_enc)
                 MXEC_TRY(new_event(&ws.summed));
                 ws.sum_tables.owner = d;
                 MXEC_TRY(ws.sum_tables.reserve(std::max<size_t>(4096, size_t(writer_sum_runs_of(w->plan, 0)) * kSumRunTables)));
             }
         }
         w->sha.resize(size_t(w->plan.k + w->m));
+        if (eo) MXEC_TRY(open_enc(*w, *eo));
         std::error_code ec;
         fs::create_directories(w->dir, ec);
         if (ec) return set_error(MXEC_E_IO, "IO error: " + ec.message());
@@ -417,15 +704,25 @@ int mxec_writer_open_sums(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size
     return open_writer(ctx, ec_dir, chunk_size, parity_shards, total_len, plaintext_size, window_bytes, which, out);
 }
 
+int mxec_writer_open_encrypted(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uint32_t parity_shards,
+                               uint64_t plaintext_len, const uint8_t key[32], const uint8_t nonce_prefix[4],
+                               const uint8_t* aad_prefix, uint32_t aad_prefix_len, uint64_t window_bytes,
+                               uint32_t which, void** out) {
+    const EncOpen eo{plaintext_len, key, nonce_prefix, aad_prefix, aad_prefix_len};
+    return open_writer(ctx, ec_dir, chunk_size, parity_shards, 0, 0, window_bytes, which, out, &eo);
+}
+
 int mxec_writer_write(void* wp, const uint8_t* buf, uint64_t len) {
     return guarded([&]() -> int {
         auto* w = static_cast<mxec_writer*>(wp);
         if (!w || (len && !buf)) return set_error(MXEC_E_INVALID_ARG, "null argument");
         if (w->err) return set_error(w->err, w->err_msg);
         if (w->finished) return set_error(MXEC_E_INVALID_ARG, "write after finish");
-        if (writer_overruns(w->plan, w->written, len))
-            return poison(*w, set_error(MXEC_E_INVALID_ARG, writer_overrun_msg(w->plan, w->written, len)));
+        const WriterPlan& body = w->enc ? w->enc->pplan : w->plan;  // the bytes the caller counts in
+        if (writer_overruns(body, w->written, len))
+            return poison(*w, set_error(MXEC_E_INVALID_ARG, writer_overrun_msg(body, w->written, len)));
         MXEC_HIP(hipSetDevice(w->dev->id));
+        if (w->enc) return poison(*w, enc_write(*w, buf, len));
         const int rc = writer_cut(w->plan, w->written, len, [&](const WriterRun& r) {
             const int e = take_run(*w, r, buf);
             if (!e) w->written += r.len;

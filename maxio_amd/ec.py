@@ -693,6 +693,16 @@ class Context:
         """which (SUM_*): the body digests ``ChunkWriter.sums()`` returns after finish()."""
         return ChunkWriter(self, ec_dir, chunk_size, parity_shards, total_len, plaintext_size, window_bytes, which)
 
+    def open_writer_encrypted(self, ec_dir: str, chunk_size: int, parity_shards: int, plaintext_len: int,
+                              key: bytes, nonce_prefix: bytes, aad_prefix: bytes, window_bytes: int = 0,
+                              which: int = 0) -> "ChunkWriter":
+        """mxec_writer_open_encrypted (put_object_chunked_encrypted,
+        filesystem.rs:835-1060, as a push stream): ``write`` takes plaintext,
+        the directory receives the frame stream's chunks, and ``sums()`` are
+        the plaintext's digests."""
+        return ChunkWriter(self, ec_dir, chunk_size, parity_shards, plaintext_len, None, window_bytes, which,
+                           encrypt=(key, nonce_prefix, aad_prefix))
+
     def body_sums(self, bodies: Sequence, which: int = 0x1F) -> list[dict]:
         """mxec_body_sums_batch: digests of host bodies (one dict each)."""
         arrs = [_u8(b) for b in bodies]
@@ -830,6 +840,27 @@ class Context:
             _check(rc)
         return [int(st[i]) for i in range(len(jobs))]
 
+    def frames_encrypt_window_device(self, job: dict, stream_off: int, base_dev: int, chunk_size: int,
+                                     slot_stride: int, slots: int, dev: int = 0, stream=None) -> None:
+        """mxec_frames_encrypt_window_device: one job (a dict as frames_device
+        takes; out_dev is ignored) whose frame stream starts at stream_off,
+        stored into the ring of ``slots`` chunk slots at base_dev."""
+        k = _u8(job["key"]) if job.get("key") is not None else None
+        j = N.FramesJob()
+        j.key = _ptr(k) if k is not None else None
+        for b, v in enumerate(job.get("nonce_prefix", b"\0\0\0\0")):
+            j.nonce_prefix[b] = v
+        j.frame_size = job.get("frame_size", FRAME_CHUNK_SIZE)
+        j.first_index = job.get("first_index", 0)
+        j.aad_dev = job.get("aad_dev") or None
+        j.aad_len = job.get("aad_len", 0)
+        j.in_dev = job.get("in_dev") or None
+        j.len = job["len"]
+        j.out_dev = None
+        win = N.FramesWindow(base_dev or None, chunk_size, slot_stride, slots)
+        _check(self._lib.mxec_frames_encrypt_window_device(self._h, dev, stream, ctypes.byref(j), stream_off,
+                                                           ctypes.byref(win)))
+
     def frame_aads(self, prefix: bytes, first_index: int, n: int) -> list[bytes]:
         """build_frame_aad for frames first_index .. first_index + n - 1."""
         if n == 0:
@@ -955,13 +986,22 @@ class ChunkWriter:
     only closes on an exception (no manifest is written then)."""
 
     def __init__(self, ctx: "Context", ec_dir: str, chunk_size: int, parity_shards: int, total_len: int,
-                 plaintext_size: Optional[int] = None, window_bytes: int = 0, which: int = 0):
+                 plaintext_size: Optional[int] = None, window_bytes: int = 0, which: int = 0, encrypt=None):
         self._lib = ctx._lib
         self._ctx = ctx  # keeps the device context alive while the writer is open
         self._w = None
         self._finished = False
         self._which = which
         h = ctypes.c_void_p()
+        path = ec_dir.encode() if ec_dir is not None else None
+        if encrypt is not None:  # (key, nonce_prefix, aad_prefix): total_len is the plaintext's
+            key, pre, ap = (None if x is None else _u8(x) for x in encrypt)
+            _check(self._lib.mxec_writer_open_encrypted(
+                ctx._h, path, chunk_size, parity_shards, total_len, None if key is None else _ptr(key),
+                None if pre is None else _ptr(pre), _ptr(ap) if ap is not None and ap.size else None,
+                0 if ap is None else ap.size, window_bytes, which, ctypes.byref(h)))
+            self._w = h
+            return
         _check(self._lib.mxec_writer_open_sums(ctx._h, ec_dir.encode() if ec_dir is not None else None, chunk_size,
                                                parity_shards, total_len,
                                                (1 << 64) - 1 if plaintext_size is None else plaintext_size,

@@ -80,6 +80,18 @@ pub struct MxecFramesJob {
     pub out_dev: *mut u8,
 }
 
+/// `mxec_frames_window`: a ring of chunk slots that the window form of the
+/// frame encryptor stores into (byte x of the frame stream at
+/// `base_dev + ((x / chunk_size) % slots) * slot_stride + x % chunk_size`).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct MxecFramesWindow {
+    pub base_dev: *mut u8,
+    pub chunk_size: u64,
+    pub slot_stride: u64,
+    pub slots: u64,
+}
+
 /// `mxec_multipart_part`: one part of CompleteMultipartUpload (PartMeta).
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -270,6 +282,8 @@ extern "C" {
     pub fn mxec_frames_encrypt(ctx: *mut MxecCtx, key: *const u8, nonce_prefix: *const u8, first_index: u64, aad: *const u8, aad_len: u32, frame_size: u32, pt: *const u8, len: u64, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
     pub fn mxec_frames_decrypt(ctx: *mut MxecCtx, key: *const u8, first_index: u64, aad: *const u8, aad_len: u32, frame_size: u32, frames: *const u8, frames_len: u64, plaintext_size: u64, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
     pub fn mxec_frames_encrypt_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, jobs: *const MxecFramesJob, n_jobs: u64) -> c_int;
+    /// `win`: a `*const MxecFramesWindow`.
+    pub fn mxec_frames_encrypt_window_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, job: *const MxecFramesJob, stream_off: u64, win: *const c_void) -> c_int;
     pub fn mxec_frames_decrypt_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, jobs: *const MxecFramesJob, n_jobs: u64, status_out: *mut i32) -> c_int;
     pub fn mxec_frame_aads(ctx: *mut MxecCtx, prefix: *const u8, prefix_len: u32, first_index: u64, n_frames: u64, out: *mut [u8; 32]) -> c_int;
     pub fn mxec_body_sums_batch(ctx: *mut MxecCtx, bodies: *const *const u8, lens: *const u64, n: u64, which: u32, out: *mut MxecBodySums) -> c_int;
@@ -284,6 +298,7 @@ extern "C" {
     pub fn mxec_get_object_chunked_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, key: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, frame_size: u32, plaintext_size: u64, offset: u64, length: u64, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
     pub fn mxec_writer_open(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, total_len: u64, plaintext_size: u64, window_bytes: u64, out: *mut *mut c_void) -> c_int;
     pub fn mxec_writer_open_sums(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, total_len: u64, plaintext_size: u64, window_bytes: u64, which: u32, out: *mut *mut c_void) -> c_int;
+    pub fn mxec_writer_open_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, plaintext_len: u64, key: *const u8, nonce_prefix: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, window_bytes: u64, which: u32, out: *mut *mut c_void) -> c_int;
     pub fn mxec_writer_write(w: *mut c_void, buf: *const u8, len: u64) -> c_int;
     pub fn mxec_writer_finish(w: *mut c_void) -> c_int;
     pub fn mxec_writer_sums(w: *mut c_void, out: *mut MxecBodySums) -> c_int;
