@@ -642,6 +642,27 @@ typedef struct mxec_frames_window mxec_frames_window;
 int mxec_frames_encrypt_window_device(mxec_ctx* ctx, int dev, void* stream,
                                       const mxec_frames_job* job, uint64_t stream_off,
                                       const void* win);
+/* The decrypt form whose source is that ring: FrameDecryptor (crypto.rs:186-420)
+ * reading verified chunks where they lie in HBM.  Byte x of the frame stream is
+ * read from base_dev + ((x / chunk_size) % slots) * slot_stride + x % chunk_size;
+ * job->out_dev receives job->len plaintext bytes, contiguous.  One job per
+ * call; job->in_dev and job->nonce_prefix are ignored.  frame_status_dev is a
+ * device array of one int32_t per frame: 0 ok, 1 tag mismatch, 2 the stored
+ * index is not first_index + f (an index mismatch takes precedence).  The
+ * plaintext of a frame whose status is not 0 is in out_dev all the same and
+ * must not be used.  A stored nonce, ciphertext and tag may each be cut by
+ * chunk boundaries, any number of times, and by the ring's wrap.  Bytes of the
+ * window outside the mapped range are never read; nothing but out_dev[0, len)
+ * and the statuses is written.  Enqueue-only on `stream`, statuses included:
+ * unlike mxec_frames_decrypt_device it does not wait, so a caller queues its
+ * downloads behind it.  MXEC_E_INVALID_ARG, decided before anything is queued:
+ * what mxec_frames_encrypt_window_device refuses (with out_dev in the place of
+ * in_dev), a null frame_status_dev with len > 0, and a job whose stream bytes
+ * exceed the window's slots * chunk_size, for its first bytes would no longer
+ * be resident.  len == 0 is MXEC_OK and does nothing. */
+int mxec_frames_decrypt_window_device(mxec_ctx* ctx, int dev, void* stream,
+                                      const mxec_frames_job* job, uint64_t stream_off,
+                                      const void* win, int32_t* frame_status_dev);
 /* build_frame_aad / build_part_aad (filesystem.rs:118-158): out[i] =
  * SHA-256(prefix || (first_index + i) as u64 LE), prefix = the identity bytes
  * (bucket 0 key 0 version 0, or "PART" 0 upload_id 0 part_le4 0). */
@@ -914,6 +935,61 @@ int mxec_reader_open(mxec_ctx* ctx, const char* ec_dir, uint64_t offset,
                      uint64_t length, uint64_t batch_bytes, mxec_reader** out);
 int64_t mxec_reader_read(mxec_reader* r, uint8_t* buf, uint64_t cap);
 void mxec_reader_close(mxec_reader* r);
+
+/* mxec_reader_open_encrypted (get_object / get_object_range of an
+ * encrypt-then-EC object, filesystem.rs:1618-1630, :1700-1725, as a pull
+ * stream: FrameDecryptor::for_range over VerifiedChunkReader,
+ * crypto.rs:186-420): the read-side counterpart of mxec_writer_open_encrypted.
+ * mxec_reader_read and mxec_reader_close take the handle unchanged.  offset
+ * and length are plaintext coordinates (length UINT64_MAX = to the end);
+ * plaintext_size = ObjectMeta.size, or UINT64_MAX for the manifest's
+ * (MXEC_E_JSON when it has none); frame_size any positive multiple of 16 below
+ * 2^31 - 256; batch_bytes as in mxec_reader_open.  The argument errors are
+ * mxec_get_object_chunked_encrypted's.
+ *
+ * Concatenated, the bytes read() returns are exactly what
+ * mxec_get_object_chunked_encrypted returns for the same arguments, for every
+ * (offset, length), every read size and every batch_bytes.
+ *
+ * Failures stream.  A frame that fails (index, tag, truncation) or an
+ * unrecoverable chunk under a frame fails the read that reaches it, after
+ * every plaintext byte of the range in front of the failing frame was
+ * returned.  Plaintext of a frame whose tag did not verify is never returned,
+ * not even partially.  After an error every later read returns it again.
+ * The chunk reader's errors are verbatim ("checksum mismatch on chunk ...",
+ * "failed to read chunk ...", size mismatch, too few shards);
+ * MXEC_E_INTEGRITY carries crypto.rs's three messages, "frame index mismatch:
+ * expected E, got G" with the stored index, which the reader fetches from HBM.
+ * Chunks with parity are repaired as the plain reader repairs them (its host
+ * path; the rebuilt chunk goes up into its slot) and decrypted after that.
+ *
+ * Data path: at open the key schedule and GHASH tables are prepared once and
+ * stay in HBM until close, when the host copies of key and tables are zeroed.
+ * The frames of the range are [offset / frame_size, (end - 1) / frame_size],
+ * whole, from FrameDecryptor::ciphertext_offset on.  A round takes the next
+ * chunks of those stream bytes up to batch_bytes (at least one), reads them
+ * from their files through two page-locked pieces (at most 1 MiB each) into
+ * their slots of a ring in HBM (chunk j in slot j % slots), hashes them where
+ * they lie and compares with the manifest.  One launch of the GCM kernel's
+ * decrypt window form (mxec_frames_decrypt_window_device) then decrypts every
+ * frame that is whole in verified chunks; its AADs are hashed on the host and
+ * go up in front of it.  The statuses come down first, then only the
+ * plaintext the range still wants (a ranged read skips the head of its first
+ * frame and the tail of its last), through one more page-locked piece as
+ * read() asks for it.  A frame cut by the round's end waits for the next
+ * round, and its chunks' slots are not reused before it is decrypted: the ring
+ * never has fewer slots than one frame can touch plus one, or all the range's
+ * chunks.  Every ciphertext byte is uploaded once.
+ * Memory: host, three page-locked pieces, the AADs and statuses of one launch;
+ * HBM, the ring (one round plus one frame of ciphertext), one launch's
+ * plaintext and 12.6 KiB of key tables.  None grows with the object.
+ * Threads: one reader is used by one thread at a time; any number of readers
+ * run concurrently on a context, each on a stream of its own. */
+int mxec_reader_open_encrypted(mxec_ctx* ctx, const char* ec_dir, const uint8_t key[32],
+                               const uint8_t* aad_prefix, uint32_t aad_prefix_len,
+                               uint32_t frame_size, uint64_t plaintext_size,
+                               uint64_t offset, uint64_t length, uint64_t batch_bytes,
+                               mxec_reader** out);
 
 /* try_reconstruct_data_chunk (chunk_reader.rs:157-226) over ec_dir's files and
  * manifest.json: out receives chunks[target].size bytes. */

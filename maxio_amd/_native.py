@@ -53,7 +53,7 @@ class FramesJob(ctypes.Structure):
 
 
 class FramesWindow(ctypes.Structure):
-    """mxec_frames_window: the ring of chunk slots of mxec_frames_encrypt_window_device."""
+    """mxec_frames_window: the ring of chunk slots of mxec_frames_{en,de}crypt_window_device."""
 
     _fields_ = [
         ("base_dev", ctypes.c_void_p),
@@ -210,6 +210,7 @@ _SIGS = {
     "mxec_frames_decrypt": (INT, [P, P, U64, P, ctypes.c_uint32, ctypes.c_uint32, P, U64, U64, P, U64, U64P]),
     "mxec_frames_encrypt_device": (INT, [P, INT, P, P, U64]),
     "mxec_frames_encrypt_window_device": (INT, [P, INT, P, P, U64, P]),
+    "mxec_frames_decrypt_window_device": (INT, [P, INT, P, P, U64, P, P]),
     "mxec_frames_decrypt_device": (INT, [P, INT, P, P, U64, ctypes.POINTER(ctypes.c_int32)]),
     "mxec_frame_aads": (INT, [P, P, ctypes.c_uint32, U64, U64, P]),
     "mxec_body_sums_batch_device": (INT, [P, INT, P, PP, U64P, U64, ctypes.c_uint32, P]),
@@ -229,6 +230,8 @@ _SIGS = {
     "mxec_writer_sums": (INT, [P, P]),
     "mxec_writer_close": (None, [P]),
     "mxec_reader_open": (INT, [P, ctypes.c_char_p, U64, U64, U64, ctypes.POINTER(ctypes.c_void_p)]),
+    "mxec_reader_open_encrypted": (INT, [P, ctypes.c_char_p, P, P, ctypes.c_uint32, ctypes.c_uint32, U64, U64, U64, U64,
+                                         ctypes.POINTER(ctypes.c_void_p)]),
     "mxec_reader_read": (ctypes.c_int64, [P, P, U64]),
     "mxec_reader_close": (None, [P]),
     "mxec_ticket_fd": (INT, [P]),

@@ -175,8 +175,9 @@ struct Job {
     uint8_t* out;        // device: frames (encrypt) / plaintext (decrypt)
 };
 
-// Where a launch's frames go when not to Job::out: the chunk ring of
-// mxec_frames_window, `off` the stream offset of the (one) job's first frame.
+// Where a launch's frame stream lies when not at Job::out (encrypt) or Job::in
+// (decrypt): the chunk ring of mxec_frames_window, `off` the stream offset of
+// the (one) job's first frame.
 struct Window {
     mxec_frames_window w;
     uint64_t off;
@@ -185,7 +186,7 @@ struct Window {
 // One launch over every frame of every job; decrypt statuses per frame land
 // in status_dev.  keys_dev: the jobs' GcmKeys already resident in HBM, one
 // per job (null: prepared here from Job::key and uploaded with the frames).
-// win (encrypt, one job): the window form.  arena: the tables from it instead
+// win (one job): the window forms.  arena: the tables from it instead
 // of the slot's ring, whose entries are fenced by events on `s` -- a caller
 // whose stream does not outlive the slot (a writer's) brings its own.
 int run_frames(Device& d, Slot& slot, hipStream_t s, const std::vector<Job>& jobs, bool decrypt,
@@ -209,7 +210,8 @@ int run_frames(Device& d, Slot& slot, hipStream_t s, const std::vector<Job>& job
             GcmFrame fr{};
             const uint64_t plen = std::min<uint64_t>(jb.frame_size, jb.len - f * jb.frame_size);
             if (win) {
-                fr.in = jb.in + f * jb.frame_size;
+                if (decrypt) fr.out = jb.out + f * jb.frame_size;
+                else fr.in = jb.in + f * jb.frame_size;
                 fr.pos = pos0 + f * fl;
             } else {
                 uint8_t* frame = const_cast<uint8_t*>(decrypt ? jb.in : jb.out) + f * fl;
@@ -254,7 +256,7 @@ int run_frames(Device& d, Slot& slot, hipStream_t s, const std::vector<Job>& job
         a.chunk_size = win->w.chunk_size;
         a.slot_stride = win->w.slot_stride;
         a.slots = win->w.slots;
-        MXEC_HIP(launch_gcm_frames_window(a, d.n_cus, s));
+        MXEC_HIP(launch_gcm_frames_window(a, decrypt, d.n_cus, s));
     } else {
         MXEC_HIP(launch_gcm_frames(a, decrypt, d.n_cus, s));
     }
@@ -280,10 +282,9 @@ int frame_error(const int32_t* st, uint64_t nf, uint64_t first_index, const uint
                 const uint8_t* h = frames_host + f * (uint64_t(fs) + MXEC_FRAME_OVERHEAD) + 4;
                 for (int j = 7; j >= 0; --j) got = (got << 8) | h[j];
             }
-            return set_error(MXEC_E_INTEGRITY, "frame index mismatch: expected " + std::to_string(first_index + f) +
-                                                   ", got " + std::to_string(got));
+            return gcm_frame_fail(2, first_index + f, got);
         }
-        if (st[f]) return set_error(MXEC_E_INTEGRITY, "AES-GCM decryption failed: authentication error");
+        if (st[f]) return gcm_frame_fail(st[f], 0, 0);
     }
     (void)plain;
     return MXEC_OK;
@@ -291,10 +292,21 @@ int frame_error(const int32_t* st, uint64_t nf, uint64_t first_index, const uint
 
 }  // namespace
 
-// The argument checks of the window form (include/maxio_ec.h
-// mxec_frames_encrypt_window_device), all before anything is queued.
-int mxec::gcm_window_check(const mxec_frames_job& q, const mxec_frames_window& w, bool need_key) {
-    if ((need_key && !q.key) || (q.len && !q.in_dev) || (q.aad_len && !q.aad_dev) || !w.base_dev)
+// A failed frame's error, as crypto.rs words it (:330-360).
+int mxec::gcm_frame_fail(int32_t status, uint64_t expected, uint64_t got) {
+    if (status == 2)
+        return set_error(MXEC_E_INTEGRITY, "frame index mismatch: expected " + std::to_string(expected) + ", got " +
+                                               std::to_string(got));
+    return set_error(MXEC_E_INTEGRITY, "AES-GCM decryption failed: authentication error");
+}
+
+// The argument checks of the window forms (include/maxio_ec.h
+// mxec_frames_encrypt_window_device, mxec_frames_decrypt_window_device), all
+// before anything is queued.  The job's other side is contiguous: in_dev for
+// encrypt, out_dev for decrypt, whose stream is read, not written.
+int mxec::gcm_window_check(const mxec_frames_job& q, const mxec_frames_window& w, bool need_key, bool decrypt) {
+    if ((need_key && !q.key) || (q.len && !(decrypt ? static_cast<const void*>(q.out_dev) : q.in_dev)) ||
+        (q.aad_len && !q.aad_dev) || !w.base_dev)
         return set_error(MXEC_E_INVALID_ARG, "null argument");
     MXEC_TRY(check_frame_size(q.frame_size));
     // The kernel's offsets within a frame are 32-bit.
@@ -309,7 +321,8 @@ int mxec::gcm_window_check(const mxec_frames_job& q, const mxec_frames_window& w
     const uint64_t span = q.len + MXEC_FRAME_OVERHEAD * nf;
     if (span > w.slots * w.chunk_size)
         return set_error(MXEC_E_INVALID_ARG, "the job's " + std::to_string(span) + " stream bytes exceed the window's " +
-                                                 std::to_string(w.slots * w.chunk_size) + ": it would overwrite itself");
+                                                 std::to_string(w.slots * w.chunk_size) +
+                                                 (decrypt ? ": its first bytes are no longer resident" : ": it would overwrite itself"));
     return MXEC_OK;
 }
 
@@ -321,6 +334,15 @@ int mxec::gcm_encrypt_window(Device& d, Slot& slot, hipStream_t s, const GcmKey*
                  nullptr};
     const Window win{w, stream_off};
     return run_frames(d, slot, s, {jb}, false, nullptr, key_dev, &win, arena);
+}
+
+// The decrypt window form's launch, likewise: the plaintext to q.out_dev, a
+// status per frame (0 ok, 1 tag, 2 index) to status_dev, both on s.
+int mxec::gcm_decrypt_window(Device& d, Slot& slot, hipStream_t s, const GcmKey* key_dev, const mxec_frames_job& q,
+                             uint64_t stream_off, const mxec_frames_window& w, int32_t* status_dev, DescArena* arena) {
+    const Job jb{q.key, 0, q.frame_size, q.first_index, q.aad_dev, q.aad_len, nullptr, q.len, q.out_dev};
+    const Window win{w, stream_off};
+    return run_frames(d, slot, s, {jb}, true, status_dev, key_dev, &win, arena);
 }
 
 extern "C" {
@@ -428,6 +450,21 @@ int mxec_frames_encrypt_window_device(mxec_ctx* ctx, int dev, void* stream, cons
         DevScope ds;
         MXEC_TRY(ds.open(ctx, dev));
         return gcm_encrypt_window(*ds.d, *ds.slot, static_cast<hipStream_t>(stream), nullptr, *job, stream_off, *win);
+    });
+}
+
+int mxec_frames_decrypt_window_device(mxec_ctx* ctx, int dev, void* stream, const mxec_frames_job* job,
+                                      uint64_t stream_off, const void* win_, int32_t* frame_status_dev) {
+    return guarded([&] {
+        const auto* win = static_cast<const mxec_frames_window*>(win_);
+        if (!job || !win) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        MXEC_TRY(gcm_window_check(*job, *win, true, true));
+        if (job->len == 0) return MXEC_OK;
+        if (!frame_status_dev) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        DevScope ds;
+        MXEC_TRY(ds.open(ctx, dev));
+        return gcm_decrypt_window(*ds.d, *ds.slot, static_cast<hipStream_t>(stream), nullptr, *job, stream_off, *win,
+                                  frame_status_dev);
     });
 }
 

@@ -219,7 +219,7 @@ __device__ __forceinline__ void store16_be(uint8_t* p, u32x4 v) {
     *reinterpret_cast<u32x4a1*>(p) = u32x4a1{bswap(v.x), bswap(v.y), bswap(v.z), bswap(v.w)};
 }
 
-// ---- the windowed destination (encrypt into a ring of chunk slots) ------------
+// ---- the window: a ring of chunk slots (encrypt into it, decrypt out of it) ----
 // One frame's view of the ring, uniform over its 256 lanes (kept in SGPRs).
 // The frame's first chunk c0 holds its first d0 bytes from p0 on; its chunk
 // c0 + t (t >= 1) starts at pa + t * stride while t < wrap and at
@@ -284,6 +284,35 @@ __device__ __forceinline__ void win_store(const WinFrame& w, uint32_t o, const u
     else win_store_bytes(w, c, v, n);
 }
 
+// The first n (<= 16) bytes from c on as big-endian words, zero padded: the
+// gather that mirrors win_store_bytes.  Exactly n bytes are read.
+__device__ __forceinline__ u32x4 win_load_bytes(const WinFrame& w, WinCursor c, uint32_t n) {
+    u32x4 v = {0u, 0u, 0u, 0u};
+#pragma unroll 1
+    for (uint32_t i = 0; i < 16; ++i) {
+        uint32_t b = 0;
+        if (i < n) {
+            if (c.room == 0) {
+                c.p = win_chunk(w, ++c.t);
+                c.room = w.cs;
+            }
+            b = *c.p++;
+            --c.room;
+        }
+        v.x = __builtin_amdgcn_alignbit(v.x, v.y, 24);
+        v.y = __builtin_amdgcn_alignbit(v.y, v.z, 24);
+        v.z = __builtin_amdgcn_alignbit(v.z, v.w, 24);
+        v.w = v.w << 8 | b;
+    }
+    return v;
+}
+// n bytes at frame offset o: one load when 16 are wanted and no boundary cuts them.
+__device__ __forceinline__ u32x4 win_load(const WinFrame& w, uint32_t o, uint32_t n) {
+    const WinCursor c = win_seek(w, o);
+    if (n == 16 && c.room >= 16) return load16_be(c.p);
+    return win_load_bytes(w, c, n);
+}
+
 // LDS: the four T-tables replicated 32 times, laid out so that a lookup's
 // address is ONE v_perm_b32 of the state word and a per-lane constant:
 //     byte offset = pair * 65536 + x * 256 + t * 128 + (lane % 32) * 4
@@ -312,14 +341,15 @@ static_assert(kGcmLdsBytes <= 160 * 1024, "GCM LDS image exceeds 160 KiB");
 
 typedef const uint32_t __attribute__((address_space(3)))* lds_u32p;
 
-// kWindow (encrypt only): the frames go to a ring of chunk slots (GcmWinArgs)
-// instead of to one contiguous run.  A frame that no chunk boundary cuts gets
-// its pointers once and runs the contiguous form's stores; a cut frame sends
-// every store through win_store.  Which it is, is uniform and held in an SGPR.
+// kWindow: the frame stream lies in a ring of chunk slots (GcmWinArgs) instead
+// of in one contiguous run -- encrypt stores it there, decrypt reads it from
+// there (the other side, plaintext, is contiguous either way).  A frame that
+// no chunk boundary cuts gets its pointers once and runs the contiguous form's
+// loads and stores; a cut frame sends every access to the stream through
+// win_store / win_load.  Which it is, is uniform and held in an SGPR.
 template <bool kDecrypt, bool kWindow = false>
 __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
     typename std::conditional<kWindow, GcmWinArgs, GcmArgs>::type a) {
-    static_assert(!(kDecrypt && kWindow), "the window form encrypts");
     extern __shared__ uint32_t smem[];
     uint32_t* te = smem;
     // The lookup addresses assume the tables start at LDS address 0.
@@ -357,8 +387,9 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
         __syncthreads();
         const uint32_t* rk = key->rk;
         const uint32_t nb = (fr.len + 15) / 16, na = (fr.aad_len + 15) / 16;
-        // Where the frame goes.
+        // Where the frame lies: header, payload in and out, tag.
         uint8_t *hdr_p = fr.hdr, *out_p = fr.out, *tag_p = fr.tag;
+        const uint8_t* in_p = fr.in;
         bool cut = false;
         WinFrame wf{};
         if constexpr (kWindow) {
@@ -375,17 +406,27 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
             wf.wrap = uniform(uint32_t(min(wrap, uint64_t(0xFFFFFFFFu))));
             cut = uniform(uint32_t(live && room < uint64_t(fr.len) + 28u)) != 0;
             hdr_p = reinterpret_cast<uint8_t*>(wf.p0);
-            out_p = hdr_p + 12;
-            tag_p = out_p + fr.len;
+            if (kDecrypt) in_p = hdr_p + 12;
+            else out_p = hdr_p + 12;
+            tag_p = hdr_p + 12 + fr.len;
         }
+        constexpr bool kWinOut = kWindow && !kDecrypt, kWinIn = kWindow && kDecrypt;
         // 16 bytes, or the partial last block's n, of the payload at offset off.
         auto put16 = [&](uint32_t off, const u32x4& v) {
-            if (kWindow && cut) win_store(wf, 12 + off, v, 16);
+            if (kWinOut && cut) win_store(wf, 12 + off, v, 16);
             else store16_be(out_p + off, v);
         };
         auto putn = [&](uint32_t off, const u32x4& v, uint32_t n) {
-            if (kWindow && cut) win_store(wf, 12 + off, v, n);
+            if (kWinOut && cut) win_store(wf, 12 + off, v, n);
             else store_partial_be(out_p + off, v, n);
+        };
+        auto get16 = [&](uint32_t off) -> u32x4 {
+            if (kWinIn && cut) return win_load(wf, 12 + off, 16);
+            return load16_be(in_p + off);
+        };
+        auto getn = [&](uint32_t off, uint32_t n) -> u32x4 {
+            if (kWinIn && cut) return win_load(wf, 12 + off, n);
+            return load_partial_be(in_p + off, n);
         };
         const uint32_t m = live ? na + nb + 1 : 0;
         // The 12-byte nonce: prefix || index (u64 LE).  Encrypt builds it and
@@ -393,7 +434,7 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
         uint32_t n0 = 0, n1 = 0, n2 = 0;
         if (live) {
             if (kDecrypt) {
-                const u32x4 h = load_partial_be(fr.hdr, 12);
+                const u32x4 h = kWinIn && cut ? win_load_bytes(wf, win_seek(wf, 0), 12) : load_partial_be(hdr_p, 12);
                 n0 = h.x; n1 = h.y; n2 = h.z;
             } else {
                 n0 = fr.prefix_be;
@@ -418,7 +459,7 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
                 aes_block(lk, rk, s0, s1, s2, s3);
 #endif
                 const u32x4 ks = {s0, s1, s2, s3};
-                u32x4 in = n == 16 ? load16_be(fr.in + off) : load_partial_be(fr.in + off, n);
+                u32x4 in = n == 16 ? get16(off) : getn(off, n);
                 u32x4 out = {in.x ^ ks.x, in.y ^ ks.y, in.z ^ ks.z, in.w ^ ks.w};
                 if (n == 16) {
                     put16(off, out);
@@ -460,7 +501,7 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
 #endif
         for (; i + 256 < full_end && i >= na; i += 512) {
             const uint32_t j0 = i - na, j1 = j0 + 256;
-            const u32x4 in0 = load16_be(fr.in + 16 * j0), in1 = load16_be(fr.in + 16 * j1);
+            const u32x4 in0 = get16(16 * j0), in1 = get16(16 * j1);
             uint32_t a0 = n0, a1 = n1, a2 = n2, a3 = 2u + j0;
             uint32_t b0 = n0, b1 = n1, b2 = n2, b3 = 2u + j1;
 #ifndef GCM_LAB_NO_AES
@@ -505,10 +546,11 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
             if (kDecrypt) {
                 // stored index (nonce bytes 4..11, LE) must be this frame's
                 const uint64_t stored = uint64_t(bswap(n1)) | uint64_t(bswap(n2)) << 32;
-                const u32x4 want = load_partial_be(fr.tag, 16);
+                const u32x4 want =
+                    kWinIn && cut ? win_load_bytes(wf, win_seek(wf, 12 + fr.len), 16) : load_partial_be(tag_p, 16);
                 const bool ok = want.x == tag.x && want.y == tag.y && want.z == tag.z && want.w == tag.w;
                 a.status[f] = stored != fr.index ? 2 : ok ? 0 : 1;
-            } else if (kWindow && cut) {  // a boundary may fall inside either
+            } else if (kWinOut && cut) {  // a boundary may fall inside either
                 win_store_bytes(wf, win_seek(wf, 0), u32x4{n0, n1, n2, 0u}, 12);
                 win_store_bytes(wf, win_seek(wf, 12 + fr.len), tag, 16);
             } else {
@@ -548,14 +590,19 @@ hipError_t launch_gcm_frames(const GcmArgs& a, bool decrypt, int n_cus, hipStrea
     return hipGetLastError();
 }
 
-hipError_t launch_gcm_frames_window(const GcmWinArgs& a, int n_cus, hipStream_t s) {
+hipError_t launch_gcm_frames_window(const GcmWinArgs& a, bool decrypt, int n_cus, hipStream_t s) {
     if (a.n_frames == 0) return hipSuccess;
-    static const hipError_t attr =
+    // Each instantiation is a kernel of its own and needs the attribute itself.
+    static const hipError_t attr_enc =
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gcm_frames_kernel<false, true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, int(kGcmLdsBytes));
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((gcm_frames_kernel<false, true>), dim3(gcm_grid(a.n_frames, n_cus)), dim3(256 * kGcmGroups),
-                       kGcmLdsBytes, s, a);
+    static const hipError_t attr_dec =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gcm_frames_kernel<true, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, int(kGcmLdsBytes));
+    if (const hipError_t attr = decrypt ? attr_dec : attr_enc; attr != hipSuccess) return attr;
+    const dim3 grid(gcm_grid(a.n_frames, n_cus)), block(256 * kGcmGroups);
+    if (decrypt) hipLaunchKernelGGL((gcm_frames_kernel<true, true>), grid, block, kGcmLdsBytes, s, a);
+    else hipLaunchKernelGGL((gcm_frames_kernel<false, true>), grid, block, kGcmLdsBytes, s, a);
     return hipGetLastError();
 }
 

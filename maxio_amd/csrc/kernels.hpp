@@ -209,7 +209,9 @@ struct GcmFrame {
     uint8_t* out;            // payload out
     union {
         uint8_t* hdr;        // encrypt: 12-byte nonce written here; decrypt: stored nonce
-        uint64_t pos;        // window form: the frame's byte offset in the frame stream; out / tag unused
+        uint64_t pos;        // window forms: the frame's byte offset in the frame stream, which is where
+                             //   hdr, the stream side of in / out and tag are found; tag is unused, and
+                             //   so is out (encrypt) or in (decrypt: out is the contiguous plaintext)
     };
     uint8_t* tag;            // encrypt: tag written here; decrypt: stored tag
     const uint8_t* aad;      // aad_len bytes (may be null when aad_len == 0)
@@ -227,8 +229,10 @@ struct GcmArgs {
     uint64_t n_frames;
 };
 hipError_t launch_gcm_frames(const GcmArgs& a, bool decrypt, int n_cus, hipStream_t s);
-// The encrypt form whose destination is a ring of chunk slots: stream byte x
-// goes to base + ((x / chunk_size) % slots) * slot_stride + x % chunk_size.
+// The forms whose frame stream lies in a ring of chunk slots: stream byte x
+// is at base + ((x / chunk_size) % slots) * slot_stride + x % chunk_size.
+// Encrypt writes the stream there from GcmFrame::in; decrypt reads it there,
+// writes the plaintext to GcmFrame::out and the frame's status to status[f].
 // Every frame's pos lies in [0, 2 * slots * chunk_size): the host rebases the
 // launch by a multiple of slots * chunk_size (the mapping has that period), so
 // a frame's slot is one division and one conditional subtract away.  A launch's
@@ -237,7 +241,7 @@ struct GcmWinArgs : GcmArgs {
     uint8_t* base;
     uint64_t chunk_size, slot_stride, slots;
 };
-hipError_t launch_gcm_frames_window(const GcmWinArgs& a, int n_cus, hipStream_t s);
+hipError_t launch_gcm_frames_window(const GcmWinArgs& a, bool decrypt, int n_cus, hipStream_t s);
 
 // ---- host <-> device copies by CU waves (copy_kernel.hip) ---------------------
 // One block of a copy batch: len bytes from src to dst (one side host memory

@@ -206,11 +206,20 @@ int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const 
 // arguments gcm_window_check has passed, enqueue-only; key_dev = that
 // resident record (q.key is then not read), or null to prepare q.key here;
 // arena = where the launch's tables go instead of the slot's ring.
+// gcm_decrypt_window: the same for mxec_frames_decrypt_window_device (checked
+// with decrypt = true: out_dev is then the contiguous side, in_dev ignored);
+// status_dev takes a status per frame, written on s like the plaintext.
+// gcm_frame_fail: MXEC_E_INTEGRITY with crypto.rs's text for a frame status
+// (2: index mismatch with both indices, else the authentication error).
 struct GcmKey;
+int gcm_frame_fail(int32_t status, uint64_t expected, uint64_t got);
 void gcm_prepare_key(const uint8_t key[32], GcmKey& out);
-int gcm_window_check(const mxec_frames_job& q, const mxec_frames_window& w, bool need_key);
+int gcm_window_check(const mxec_frames_job& q, const mxec_frames_window& w, bool need_key, bool decrypt = false);
 int gcm_encrypt_window(Device& d, Slot& slot, hipStream_t s, const GcmKey* key_dev, const mxec_frames_job& q,
                        uint64_t stream_off, const mxec_frames_window& w, DescArena* arena = nullptr);
+int gcm_decrypt_window(Device& d, Slot& slot, hipStream_t s, const GcmKey* key_dev, const mxec_frames_job& q,
+                       uint64_t stream_off, const mxec_frames_window& w, int32_t* status_dev,
+                       DescArena* arena = nullptr);
 
 // Creates the device's host-pipeline hub and its streams (pipe_hub.cpp),
 // called by mxec_open for every device.

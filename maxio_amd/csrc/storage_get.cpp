@@ -7,29 +7,13 @@
 #include <cstring>
 #include <memory>
 
+#include "chunk_reader.hpp"
 #include "ops.hpp"
 #include "shard_set.hpp"
 
 using namespace mxec;
 
 namespace {
-
-struct LoadedChunk {
-    Bytes data;
-    // When set, the chunk's bytes go straight to this caller buffer of
-    // exactly the manifest's size instead of `data` (one-shot GET: the chunk
-    // lands where it is served, no intermediate copy).
-    uint8_t* dst = nullptr;
-    uint64_t dst_size = 0;  // the file's size as read into dst
-    int err = MXEC_OK;  // non-zero: this chunk fails the read that reaches it
-    std::string msg;
-    const uint8_t* ptr() const { return dst ? dst : data.data(); }
-    uint64_t size() const { return dst ? dst_size : data.size(); }
-    void fail(int code, const std::string& why) {
-        err = code;
-        msg = why;
-    }
-};
 
 // load_chunk_sync (:87-152) for chunks [first, last]: read, size check, one
 // batched digest pass; with parity every bad chunk is rebuilt in one decode
@@ -183,30 +167,18 @@ struct RangeLoad {
     }
 };
 
-// Chunks [first, last] of the object into `out`; `dsts` (optional, one per
-// chunk, nullptr = none) places chunks in caller memory (LoadedChunk::dst).
-int load_chunks(mxec_ctx* ctx, const fs::path& dir, const Manifest& man, uint32_t first, uint32_t last,
-                std::vector<LoadedChunk>& out, uint8_t* const* dsts = nullptr) {
-    out.assign(last - first + 1, LoadedChunk{});
-    for (size_t c = 0; dsts && c < out.size(); ++c) out[c].dst = dsts[c];
-    return RangeLoad{ctx, dir, man, first, last, out, {}, {}, {}, false}.run();
-}
-
 // Bytes served from a chunk of `size` bytes from offset `from` on, `left` still wanted.
 uint64_t served(uint64_t size, uint64_t from, uint64_t left) { return std::min(size > from ? size - from : 0, left); }
 
 }  // namespace
 
-struct mxec_reader {
-    mxec_ctx* ctx = nullptr;
-    fs::path dir;
-    Manifest man;
-    uint32_t next = 0, end = 0;  // next chunk to load, last chunk of the range
-    uint64_t skip = 0, remaining = 0, batch_bytes = 0;
-    std::vector<LoadedChunk> batch;
-    size_t bi = 0;
-    uint64_t pos = 0;
-};
+// chunk_reader.hpp declares it: the encrypted reader's degraded path is this one.
+int mxec::load_chunks(mxec_ctx* ctx, const fs::path& dir, const Manifest& man, uint32_t first, uint32_t last,
+                      std::vector<LoadedChunk>& out, uint8_t* const* dsts) {
+    out.assign(last - first + 1, LoadedChunk{});
+    for (size_t c = 0; dsts && c < out.size(); ++c) out[c].dst = dsts[c];
+    return RangeLoad{ctx, dir, man, first, last, out, {}, {}, {}, false}.run();
+}
 
 extern "C" {
 
@@ -240,6 +212,7 @@ int mxec_reader_open(mxec_ctx* ctx, const char* ec_dir, uint64_t offset, uint64_
 int64_t mxec_reader_read(mxec_reader* r, uint8_t* buf, uint64_t cap) {
     return guarded([&]() -> int64_t {
         if (!r || (cap && !buf)) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        if (r->enc) return enc_reader_read(*r->enc, buf, cap);
         uint64_t copied = 0;
         while (copied < cap && r->remaining > 0) {
             if (r->bi >= r->batch.size()) {

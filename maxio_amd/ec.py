@@ -688,6 +688,16 @@ class Context:
                     batch_bytes: int = 0) -> "ChunkReader":
         return ChunkReader(self, ec_dir, offset, length, batch_bytes)
 
+    def open_reader_encrypted(self, ec_dir: str, key: bytes, aad_prefix: bytes, offset: int = 0,
+                              length: Optional[int] = None, plaintext_size: Optional[int] = None,
+                              frame_size: int = 65536, batch_bytes: int = 0) -> "ChunkReader":
+        """mxec_reader_open_encrypted: get_object_chunked_encrypted as a pull
+        stream (FrameDecryptor over VerifiedChunkReader).  ``read`` returns
+        plaintext of the range; a bad frame or an unrecoverable chunk raises
+        from the read that reaches it, after the plaintext before it."""
+        return ChunkReader(self, ec_dir, offset, length, batch_bytes,
+                           decrypt=(key, aad_prefix, plaintext_size, frame_size))
+
     def open_writer(self, ec_dir: str, chunk_size: int, parity_shards: int, total_len: int,
                     plaintext_size: Optional[int] = None, window_bytes: int = 0, which: int = 0) -> "ChunkWriter":
         """which (SUM_*): the body digests ``ChunkWriter.sums()`` returns after finish()."""
@@ -861,6 +871,28 @@ class Context:
         _check(self._lib.mxec_frames_encrypt_window_device(self._h, dev, stream, ctypes.byref(j), stream_off,
                                                            ctypes.byref(win)))
 
+    def frames_decrypt_window_device(self, job: dict, stream_off: int, base_dev: int, chunk_size: int,
+                                     slot_stride: int, slots: int, status_dev: int, dev: int = 0,
+                                     stream=None) -> None:
+        """mxec_frames_decrypt_window_device: one job (a dict as frames_device
+        takes; in_dev and nonce_prefix are ignored) whose frame stream starts
+        at stream_off in the ring of ``slots`` chunk slots at base_dev; the
+        plaintext goes to out_dev, one int32 status per frame (0 ok, 1 tag,
+        2 index) to status_dev.  Enqueue-only."""
+        k = _u8(job["key"]) if job.get("key") is not None else None
+        j = N.FramesJob()
+        j.key = _ptr(k) if k is not None else None
+        j.frame_size = job.get("frame_size", FRAME_CHUNK_SIZE)
+        j.first_index = job.get("first_index", 0)
+        j.aad_dev = job.get("aad_dev") or None
+        j.aad_len = job.get("aad_len", 0)
+        j.in_dev = None
+        j.len = job["len"]
+        j.out_dev = job.get("out_dev") or None
+        win = N.FramesWindow(base_dev or None, chunk_size, slot_stride, slots)
+        _check(self._lib.mxec_frames_decrypt_window_device(self._h, dev, stream, ctypes.byref(j), stream_off,
+                                                           ctypes.byref(win), status_dev or None))
+
     def frame_aads(self, prefix: bytes, first_index: int, n: int) -> list[bytes]:
         """build_frame_aad for frames first_index .. first_index + n - 1."""
         if n == 0:
@@ -947,13 +979,21 @@ class ChunkReader:
     bytes before that chunk have been returned by earlier reads."""
 
     def __init__(self, ctx: "Context", ec_dir: str, offset: int = 0, length: Optional[int] = None,
-                 batch_bytes: int = 0):
+                 batch_bytes: int = 0, decrypt: Optional[tuple] = None):
         self._lib = ctx._lib
         self._ctx = ctx  # keeps the device context alive while the reader is open
+        self._r = None
         h = ctypes.c_void_p()
-        _check(self._lib.mxec_reader_open(ctx._h, ec_dir.encode(), offset,
-                                          (1 << 64) - 1 if length is None else length,
-                                          batch_bytes, ctypes.byref(h)))
+        ln = (1 << 64) - 1 if length is None else length
+        if decrypt is None:
+            _check(self._lib.mxec_reader_open(ctx._h, ec_dir.encode(), offset, ln, batch_bytes, ctypes.byref(h)))
+        else:  # Context.open_reader_encrypted: read() returns plaintext
+            key, aad_prefix, plaintext_size, frame_size = decrypt
+            k, ap = _u8(key), _u8(aad_prefix)
+            _check(self._lib.mxec_reader_open_encrypted(
+                ctx._h, ec_dir.encode(), _ptr(k), _ptr(ap) if ap.size else None, ap.size, frame_size,
+                (1 << 64) - 1 if plaintext_size is None else plaintext_size, offset, ln, batch_bytes,
+                ctypes.byref(h)))
         self._r = h
 
     def read(self, n: int = 1 << 20) -> bytes:

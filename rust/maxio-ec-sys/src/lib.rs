@@ -81,7 +81,7 @@ pub struct MxecFramesJob {
 }
 
 /// `mxec_frames_window`: a ring of chunk slots that the window form of the
-/// frame encryptor stores into (byte x of the frame stream at
+/// frame encryptor stores into and of the frame decryptor reads from (byte x of the frame stream at
 /// `base_dev + ((x / chunk_size) % slots) * slot_stride + x % chunk_size`).
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -284,6 +284,7 @@ extern "C" {
     pub fn mxec_frames_encrypt_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, jobs: *const MxecFramesJob, n_jobs: u64) -> c_int;
     /// `win`: a `*const MxecFramesWindow`.
     pub fn mxec_frames_encrypt_window_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, job: *const MxecFramesJob, stream_off: u64, win: *const c_void) -> c_int;
+    pub fn mxec_frames_decrypt_window_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, job: *const MxecFramesJob, stream_off: u64, win: *const c_void, frame_status_dev: *mut i32) -> c_int;
     pub fn mxec_frames_decrypt_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, jobs: *const MxecFramesJob, n_jobs: u64, status_out: *mut i32) -> c_int;
     pub fn mxec_frame_aads(ctx: *mut MxecCtx, prefix: *const u8, prefix_len: u32, first_index: u64, n_frames: u64, out: *mut [u8; 32]) -> c_int;
     pub fn mxec_body_sums_batch(ctx: *mut MxecCtx, bodies: *const *const u8, lens: *const u64, n: u64, which: u32, out: *mut MxecBodySums) -> c_int;
@@ -304,6 +305,7 @@ extern "C" {
     pub fn mxec_writer_sums(w: *mut c_void, out: *mut MxecBodySums) -> c_int;
     pub fn mxec_writer_close(w: *mut c_void);
     pub fn mxec_reader_open(ctx: *mut MxecCtx, ec_dir: *const c_char, offset: u64, length: u64, batch_bytes: u64, out: *mut *mut MxecReader) -> c_int;
+    pub fn mxec_reader_open_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, key: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, frame_size: u32, plaintext_size: u64, offset: u64, length: u64, batch_bytes: u64, out: *mut *mut MxecReader) -> c_int;
     pub fn mxec_reader_read(r: *mut MxecReader, buf: *mut u8, cap: u64) -> i64;
     pub fn mxec_reader_close(r: *mut MxecReader);
     /// `out`: a `*mut MxecScrubReport`.
