@@ -226,7 +226,14 @@ int mxec_encode(mxec_ctx* ctx, int k, int m, size_t shard_size,
  * shards are rebuilt (all of them, or data only with MXEC_F_DATA_ONLY);
  * present_inout[i] is 1 on return for every verified or rebuilt shard.
  * Fewer than k verified shards: MXEC_E_TOO_FEW_SHARDS_PRESENT, nothing is
- * written, and *n_present (if not NULL) holds the verified count. */
+ * written, and *n_present (if not NULL) holds the verified count.
+ * Shape: this and every other reconstruct entry point take what
+ * ReedSolomon::new takes, k + m <= 256 (mxec_rs_check), so a stripe of 256
+ * shards written elsewhere is rebuilt like any other, shard index 255 among
+ * the missing or among the inputs (tests/test_wide_stripes_gpu.py); 257 and
+ * more are MXEC_E_TOO_MANY_SHARDS.  The encodes, verifies and locates stop
+ * at k + m = 255 with MXEC_E_TOO_MANY_SHARDS_255, as filesystem.rs:1095
+ * does, so no 256-shard stripe comes from this library. */
 int mxec_reconstruct(mxec_ctx* ctx, int k, int m, size_t shard_size,
                      uint8_t* const* shards, const size_t* shard_len,
                      const uint8_t (*expected_sha256)[32],

@@ -19,7 +19,12 @@
 * the reconstructs' decode table builder puts every object with shards to
   rebuild exactly once under its number of rebuilt shards, its rows inside the
   returned tables with the windowed pointers, lengths and shard size, for both
-  shard-location forms (decode_tables.hpp)."""
+  shard-location forms (decode_tables.hpp);
+* the host GF(2^8) algebra (gf256.cpp: the v_perm coefficient tables, the
+  encoding matrix, the decode plans) equals the oracle's at the wide shapes
+  of test_wide_stripes_gpu.py and at 256 shards (gf256_check.cpp, built with
+  gf256.cpp; the oracle's C sources are compiled beside it as plain -O2
+  objects: they are the checker, and instrumented they take a minute)."""
 from __future__ import annotations
 
 import os
@@ -30,17 +35,26 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.join(ROOT, "tests", "c_manifest")
+# What a check is built from besides its own file: product sources under the
+# sanitizers with it, oracle sources as plain objects.
+WITH = {"gf256_check.cpp": {"cpp": ["maxio_amd/csrc/gf256.cpp"],
+                            "oracle": ["oracle/rs_oracle.c", "oracle/sha256_oracle.c"]}}
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 @pytest.mark.parametrize("src,ok", [("sha_guard_check.cpp", "sha guard ok"), ("deal_check.cpp", "deal ok"),
                                     ("piece_grid_check.cpp", "piece grid ok"), ("wave_cut_check.cpp", "wave cut ok"),
                                     ("rs_plan_check.cpp", "rs plan ok"),
-                                    ("decode_tables_check.cpp", "decode tables ok")])
+                                    ("decode_tables_check.cpp", "decode tables ok"),
+                                    ("gf256_check.cpp", "gf256 ok")])
 def test_host_planning(tmp_path, src, ok):
     exe = str(tmp_path / src.split(".")[0])
+    more = [os.path.join(ROOT, p) for p in WITH.get(src, {}).get("cpp", [])]
+    for p in WITH.get(src, {}).get("oracle", []):
+        more.append(str(tmp_path / (os.path.basename(p) + ".o")))
+        subprocess.run(["g++", "-x", "c", "-std=c11", "-O2", "-c", os.path.join(ROOT, p), "-o", more[-1]], check=True)
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", os.path.join(HERE, src), "-o", exe], check=True)
+                    "-fno-sanitize-recover=all", os.path.join(HERE, src)] + more + ["-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert ok in r.stdout
