@@ -1018,7 +1018,9 @@ int mxec_try_reconstruct_data_chunk(mxec_ctx* ctx, const char* ec_dir,
  *                               for an object without parity or with a
  *                               missing / wrong-sized file;
  *           MXEC_SCRUB_DIGESTS  SHA-256 of every present shard, parity
- *                               included, against the manifest;
+ *                               included, against the manifest (as the GET
+ *                               compares: a recorded digest that is not 64
+ *                               lower-case hex digits matches nothing);
  *           MXEC_SCRUB_HEAL     implies DIGESTS; 1 <= damaged <= m: every
  *                               damaged shard, data and parity, is rebuilt
  *                               from the verified ones, hashed, and -- only
@@ -1068,7 +1070,7 @@ int mxec_scrub_object(mxec_ctx* ctx, const char* ec_dir, uint32_t flags, void* o
  *           from the others, the rebuilt shard alone is hashed against the
  *           manifest's digest, and on equality written like a scrub's heal
  *           (temporary name, fsync, rename): healed = 1.  On disagreement,
- *           or a digest that does not parse, nothing is created, changed or
+ *           or a digest that is not 64 lower-case hex digits, nothing is created, changed or
  *           removed and healed = 0: fall back to the scrub's HEAL.
  * Returns MXEC_OK whenever the pass ran; manifest, I/O and RS-init errors as
  * from mxec_scrub_object; unknown flags MXEC_E_INVALID_ARG.  `out` points at

@@ -38,6 +38,8 @@ bool unhex32(const std::string& s, uint8_t* out) {
     return true;
 }
 
+bool manifest_digest32(const std::string& s, uint8_t* out) { return unhex32(s, out) && hex(out, 32) == s; }
+
 std::string chunk_name(uint32_t index) {
     char b[32];
     std::snprintf(b, sizeof b, "%06u", index);

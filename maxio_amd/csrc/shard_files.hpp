@@ -27,6 +27,12 @@ namespace fs = std::filesystem;
 
 std::string hex(const uint8_t* d, size_t n);       // lower case, 2n characters
 bool unhex32(const std::string& s, uint8_t* out);  // 64 hex digits of either case
+// A manifest's recorded digest as the bytes a computed one is compared with.
+// The reference compares strings, hex::encode(hash) != chunk_info.sha256
+// (chunk_reader.rs:108-109, :184-185), so only the 64 lower-case digits hex()
+// produces can ever match: anything else (upper case included) is false, and
+// the caller treats the shard as one whose digest never matches.
+bool manifest_digest32(const std::string& s, uint8_t* out);
 std::string chunk_name(uint32_t index);            // "{index:06}"
 
 // Byte buffers whose resize() leaves new bytes uninitialised: a chunk about

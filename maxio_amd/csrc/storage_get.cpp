@@ -121,8 +121,10 @@ struct RangeLoad {
                 have = loaded[size_t(i)];  // then where read_extra put it
                 if (!have) set.blank(i, false);
             }
-            if (have && verify && !unhex32(man.chunks[size_t(i)].sha256, &expected[size_t(i) * 32]))
-                have = false;  // an unparsable digest never matches
+            // As hash_pass compares, and chunk_reader.rs:108-109, :184-185: the
+            // lower-case hex string.  Any other digest never matches.
+            if (have && verify && !manifest_digest32(man.chunks[size_t(i)].sha256, &expected[size_t(i) * 32]))
+                have = false;
             set.present[size_t(i)] = have;
         }
         int np = 0;

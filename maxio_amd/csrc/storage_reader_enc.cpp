@@ -89,6 +89,9 @@ struct mxec::EncReader {
         if (!dev) return;
         (void)hipSetDevice(dev->id);
         if (s) (void)hipStreamSynchronize(s);
+        // The chunk hashes took their tables from the slots' rings, fenced by
+        // events on the stream destroyed below (as the writer's, storage_writer.cpp).
+        if (s) slots_settle(*dev);
         if (key_dev.p) (void)hipMemset(key_dev.p, 0, sizeof(GcmKey));
         for (hipEvent_t e : staged)
             if (e) (void)hipEventDestroy(e);

@@ -19,13 +19,14 @@ extern "C" int mxec_try_reconstruct_data_chunk(mxec_ctx* ctx, const char* ec_dir
         if (target >= man.chunk_count) return set_error(MXEC_E_INVALID_INDEX, "target is not a data chunk");
         // Read every shard, verify it against the manifest digest, rebuild
         // the rest on the GPU.  Present shards are hashed over their on-disk
-        // bytes, want(i) of them; a digest that does not parse can never
-        // match, so that shard is an erasure too.
+        // bytes, want(i) of them; a digest that is not the 64 lower-case
+        // digits the reference's string compare can match (chunk_reader.rs:
+        // 184-185) never matches, so that shard is an erasure too.
         ShardSet set;
         MXEC_TRY(set.open(man, ShardSet::kCheckAlways));
         std::vector<uint8_t> expected(size_t(set.total) * 32, 0);
         for (int i = 0; i < set.total; ++i)
-            if (!(set.read(ec_dir, i) && unhex32(man.chunks[size_t(i)].sha256, &expected[size_t(i) * 32])))
+            if (!(set.read(ec_dir, i) && manifest_digest32(man.chunks[size_t(i)].sha256, &expected[size_t(i) * 32])))
                 set.blank(i, true);
         int np = 0;
         MXEC_TRY(set.decode(ctx, expected.data(), 0, &np));
@@ -122,9 +123,9 @@ extern "C" int mxec_scrub_object(mxec_ctx* ctx, const char* ec_dir, uint32_t fla
             std::vector<size_t> hl;
             std::vector<int> hi;
             for (int i = 0; i < total; ++i) {
-                parsed[size_t(i)] = unhex32(man.chunks[size_t(i)].sha256, &expected[size_t(i) * 32]);
+                parsed[size_t(i)] = manifest_digest32(man.chunks[size_t(i)].sha256, &expected[size_t(i) * 32]);
                 if (st[i] != MXEC_SHARD_OK) continue;
-                if (!parsed[size_t(i)]) {  // a digest that does not parse can never match
+                if (!parsed[size_t(i)]) {  // not what the GET's string compare can match (chunk_reader.rs:108-109)
                     st[i] = MXEC_SHARD_BAD_DIGEST;
                     continue;
                 }
@@ -189,7 +190,7 @@ extern "C" int mxec_locate_object(mxec_ctx* ctx, const char* ec_dir, uint32_t fl
 
         const std::vector<int> bad{int(rep->shard)};
         std::vector<uint8_t> expected(size_t(ob.total) * 32, 0), parsed(static_cast<size_t>(ob.total), 0);
-        parsed[rep->shard] = unhex32(man.chunks[rep->shard].sha256, &expected[size_t(rep->shard) * 32]);
+        parsed[rep->shard] = manifest_digest32(man.chunks[rep->shard].sha256, &expected[size_t(rep->shard) * 32]);
         if (!parsed[rep->shard]) return MXEC_OK;  // nothing to check a rebuild against
         size_t wrote = 0;  // 0 when more is wrong than one shard: the scrub's heal
         MXEC_TRY(rebuild_and_replace(ctx, dir, ob, bad, expected, parsed, &wrote));

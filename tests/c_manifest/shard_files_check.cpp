@@ -95,6 +95,13 @@ int main(int argc, char** argv) {
     CHECK(unhex32(upper, back) && std::memcmp(raw, back, 32) == 0);
     CHECK(!unhex32(h.substr(0, 63), back));
     CHECK(!unhex32(h.substr(0, 63) + "g", back));
+    // manifest_digest32: only what hex() writes (the reference compares strings).
+    std::memset(back, 0, 32);
+    CHECK(manifest_digest32(h, back) && std::memcmp(raw, back, 32) == 0);
+    std::string one_upper = h;
+    one_upper[0] = 'A';
+    CHECK(!manifest_digest32(upper, back) && !manifest_digest32(one_upper, back));
+    CHECK(!manifest_digest32(h.substr(0, 63), back) && !manifest_digest32(h + "0", back));
     CHECK(chunk_name(7) == "000007" && chunk_name(1234567) == "1234567");
 
     // read_manifest: what it accepts, bytes that are not UTF-8, chunks
