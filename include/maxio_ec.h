@@ -670,6 +670,39 @@ int mxec_frames_encrypt_window_device(mxec_ctx* ctx, int dev, void* stream,
 int mxec_frames_decrypt_window_device(mxec_ctx* ctx, int dev, void* stream,
                                       const mxec_frames_job* job, uint64_t stream_off,
                                       const void* win, int32_t* frame_status_dev);
+/* The decrypt form whose plaintext side is a byte ring: FrameDecryptor
+ * (crypto.rs:186-420) over the frames of multipart parts, writing straight into
+ * the plaintext ring a streaming re-encryption reads
+ * (complete_multipart_chunked_encrypted, filesystem.rs:1375-1387).  Any number
+ * of jobs, each with its own key, AADs and first_index; jobs[j].in_dev is job
+ * j's contiguous frame stream from first_index on, jobs[j].out_dev and
+ * nonce_prefix are ignored.  Plaintext byte o of job j is stored at
+ *     base_dev + (ring_off[j] + o) % bytes,
+ * so a job may start at any byte of the ring and the ring's wrap may cut a
+ * frame anywhere: inside a 16-byte block, on a block or frame boundary, in the
+ * partial last block.  frame_status_dev is a device array of one int32_t per
+ * frame, in job order: 0 ok, 1 tag mismatch, 2 the stored index is not
+ * first_index + f (an index mismatch takes precedence).  The plaintext of a
+ * frame whose status is not 0 is in the ring all the same and must not be
+ * used.  Nothing past base_dev + bytes and nothing in the ring outside the
+ * jobs' ranges is written.  The ranges of one call must not overlap: that is
+ * the caller's contract.  Enqueue-only on `stream`, statuses included.
+ * MXEC_E_INVALID_ARG, decided before anything is queued: a null jobs with
+ * n_jobs > 0; a null ring, base_dev, ring_off, key, in_dev with len > 0 or
+ * aad_dev with aad_len > 0; bytes == 0; a ring_off[j] >= bytes; a frame_size
+ * that is 0, no multiple of 16 or above 2^31 - 256; a null frame_status_dev
+ * when a job has frames; the jobs' len summing to more than bytes, for the call
+ * would overwrite itself.  n_jobs == 0, or every len == 0, is MXEC_OK and does
+ * nothing.  `ring` points at a mxec_frames_ring, passed as const void*. */
+struct mxec_frames_ring {
+    uint8_t* base_dev;      /* byte 0 of the ring, any alignment */
+    uint64_t bytes;         /* > 0, any value                    */
+};
+typedef struct mxec_frames_ring mxec_frames_ring;
+int mxec_frames_decrypt_ring_device(mxec_ctx* ctx, int dev, void* stream,
+                                    const mxec_frames_job* jobs, uint64_t n_jobs,
+                                    const uint64_t* ring_off, const void* ring,
+                                    int32_t* frame_status_dev);
 /* build_frame_aad / build_part_aad (filesystem.rs:118-158): out[i] =
  * SHA-256(prefix || (first_index + i) as u64 LE), prefix = the identity bytes
  * (bucket 0 key 0 version 0, or "PART" 0 upload_id 0 part_le4 0). */
@@ -778,6 +811,52 @@ int mxec_complete_multipart_chunked_encrypted(mxec_ctx* ctx, const char* ec_dir,
                                               const uint8_t key[32], const uint8_t nonce_prefix[4],
                                               const uint8_t* aad_prefix, uint32_t aad_prefix_len,
                                               char etag_out[48]);
+
+/* The two completions above as streams (the reference's loops hold one I/O
+ * buffer, one frame and one chunk): no part and no body is buffered.  After
+ * MXEC_OK ec_dir holds byte for byte the files and manifest.json the buffered
+ * call writes for the same arguments, and etag_out the same string.
+ * window_bytes is the writer's (mxec_writer_open below); 0 is the default.
+ *
+ * Every part file is opened and its size taken first (and closed again: the
+ * feed holds open only the files one step draws from).  The body's length is
+ * the sum of the plain parts' file sizes (part.size is ignored for a plain
+ * part, as in the reference and the buffered call) and the encrypted parts'
+ * `size`.  Decided before anything is created: a missing file (MXEC_E_IO); an
+ * encrypted part without upload_key / upload_id, or given to the plain call
+ * (MXEC_E_INVALID_ARG, the buffered texts); an encrypted part whose file is
+ * shorter than mxec_frames_len(size, 65536) (MXEC_E_INTEGRITY "truncated
+ * encrypted frame"; trailing bytes are ignored); the writer's own open errors
+ * (chunk_size == 0, k + m > 255).  A part file that yields fewer bytes than
+ * its size said is MXEC_E_IO.
+ *
+ * mxec_complete_multipart_streamed reads each part in pieces of at most 1 MiB
+ * into mxec_writer_write.  The encrypted call opens mxec_writer_open_encrypted
+ * over the body's length; a plain part goes through that writer's host path;
+ * an encrypted part's frames go up, 16 at a time, into a ciphertext bounce in
+ * HBM, and one launch of mxec_frames_decrypt_ring_device per 16 frames --
+ * shared by consecutive encrypted parts, one job per part -- decrypts them
+ * under the upload key straight into the writer's plaintext ring at the body
+ * offset, where the writer's encrypt launches find them: the plaintext never
+ * exists on the host and crosses no bus.  Mixed parts are allowed
+ * (filesystem.rs:1375-1387).  The frame statuses come down behind each launch
+ * and are all checked before any parity file or the manifest is written: a
+ * bad frame is MXEC_E_INTEGRITY with mxec_frames_decrypt's texts.
+ * On any failure after the writer opened no manifest.json exists; chunk files
+ * written so far may remain, as after the reference's loop.
+ * Memory: host, the writer's pieces, two page-locked ciphertext pieces of
+ * 16 frames (1 049 024 bytes) each, one 1 MiB read buffer and the manifest's
+ * entries; HBM, the writer's, plus the 2.1 MB ciphertext bounce and a second
+ * 12.6 KiB key table.  None grows with the object. */
+int mxec_complete_multipart_streamed(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size,
+                                     uint32_t parity_shards, const mxec_multipart_part* parts,
+                                     uint32_t n_parts, uint64_t window_bytes, char etag_out[48]);
+int mxec_complete_multipart_streamed_encrypted(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size,
+                                     uint32_t parity_shards, const mxec_multipart_part* parts,
+                                     uint32_t n_parts, const uint8_t upload_key[32], const char* upload_id,
+                                     const uint8_t key[32], const uint8_t nonce_prefix[4],
+                                     const uint8_t* aad_prefix, uint32_t aad_prefix_len,
+                                     uint64_t window_bytes, char etag_out[48]);
 
 /* put_object_chunked (filesystem.rs:686-773) as a push stream: the body is
  * written in pieces of any size and never buffered whole -- the write-side

@@ -63,6 +63,15 @@ class FramesWindow(ctypes.Structure):
     ]
 
 
+class FramesRing(ctypes.Structure):
+    """mxec_frames_ring: the plaintext byte ring of mxec_frames_decrypt_ring_device."""
+
+    _fields_ = [
+        ("base_dev", ctypes.c_void_p),
+        ("bytes", ctypes.c_uint64),
+    ]
+
+
 class ChunkInfo(ctypes.Structure):
     """mxec_chunk_info == the reference's ChunkInfo (storage/mod.rs:182-189)."""
 
@@ -205,12 +214,18 @@ _SIGS = {
     "mxec_complete_multipart_chunked_encrypted": (
         INT, [P, ctypes.c_char_p, U64, ctypes.c_uint32, ctypes.POINTER(MultipartPart), ctypes.c_uint32, P,
               ctypes.c_char_p, P, P, P, ctypes.c_uint32, ctypes.c_char_p]),
+    "mxec_complete_multipart_streamed": (INT, [P, ctypes.c_char_p, U64, ctypes.c_uint32,
+                                               ctypes.POINTER(MultipartPart), ctypes.c_uint32, U64, ctypes.c_char_p]),
+    "mxec_complete_multipart_streamed_encrypted": (
+        INT, [P, ctypes.c_char_p, U64, ctypes.c_uint32, ctypes.POINTER(MultipartPart), ctypes.c_uint32, P,
+              ctypes.c_char_p, P, P, P, ctypes.c_uint32, U64, ctypes.c_char_p]),
     "mxec_frames_len": (U64, [U64, ctypes.c_uint32]),
     "mxec_frames_encrypt": (INT, [P, P, P, U64, P, ctypes.c_uint32, ctypes.c_uint32, P, U64, P, U64, U64P]),
     "mxec_frames_decrypt": (INT, [P, P, U64, P, ctypes.c_uint32, ctypes.c_uint32, P, U64, U64, P, U64, U64P]),
     "mxec_frames_encrypt_device": (INT, [P, INT, P, P, U64]),
     "mxec_frames_encrypt_window_device": (INT, [P, INT, P, P, U64, P]),
     "mxec_frames_decrypt_window_device": (INT, [P, INT, P, P, U64, P, P]),
+    "mxec_frames_decrypt_ring_device": (INT, [P, INT, P, P, U64, U64P, P, P]),
     "mxec_frames_decrypt_device": (INT, [P, INT, P, P, U64, ctypes.POINTER(ctypes.c_int32)]),
     "mxec_frame_aads": (INT, [P, P, ctypes.c_uint32, U64, U64, P]),
     "mxec_body_sums_batch_device": (INT, [P, INT, P, PP, U64P, U64, ctypes.c_uint32, P]),

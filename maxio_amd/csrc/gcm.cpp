@@ -173,6 +173,7 @@ struct Job {
     const uint8_t* in;   // device: plaintext (encrypt) / frames (decrypt)
     uint64_t len;        // plaintext bytes
     uint8_t* out;        // device: frames (encrypt) / plaintext (decrypt)
+    uint64_t ring_off = 0;  // ring form: where its plaintext starts in the ring, in the place of out
 };
 
 // Where a launch's frame stream lies when not at Job::out (encrypt) or Job::in
@@ -189,9 +190,12 @@ struct Window {
 // win (one job): the window forms.  arena: the tables from it instead
 // of the slot's ring, whose entries are fenced by events on `s` -- a caller
 // whose stream does not outlive the slot (a writer's) brings its own.
+// ring (decrypt): the ring form -- the jobs' streams are contiguous at Job::in
+// and their plaintext goes to the ring from Job::ring_off on.  one_key: every
+// job runs under keys_dev[0].
 int run_frames(Device& d, Slot& slot, hipStream_t s, const std::vector<Job>& jobs, bool decrypt,
                int32_t* status_dev, const GcmKey* keys_dev = nullptr, const Window* win = nullptr,
-               DescArena* arena = nullptr) {
+               DescArena* arena = nullptr, const mxec_frames_ring* ring = nullptr, bool one_key = false) {
     std::vector<GcmFrame> frames;
     std::vector<GcmKey> keys(keys_dev ? 0 : jobs.size());
     // The window mapping has period slots * chunk_size: the launch is rebased
@@ -217,7 +221,12 @@ int run_frames(Device& d, Slot& slot, hipStream_t s, const std::vector<Job>& job
                 uint8_t* frame = const_cast<uint8_t*>(decrypt ? jb.in : jb.out) + f * fl;
                 fr.hdr = frame;
                 fr.tag = frame + 12 + plen;
-                if (decrypt) {
+                if (ring) {
+                    // jb.ring_off < bytes and f * frame_size < jb.len <= bytes: one conditional subtract.
+                    const uint64_t x = f * jb.frame_size, room = ring->bytes - jb.ring_off;
+                    fr.in = frame + 12;
+                    fr.ring_off = x >= room ? x - room : jb.ring_off + x;
+                } else if (decrypt) {
                     fr.in = frame + 12;
                     fr.out = jb.out + f * jb.frame_size;
                 } else {
@@ -229,7 +238,7 @@ int run_frames(Device& d, Slot& slot, hipStream_t s, const std::vector<Job>& job
             fr.aad_len = jb.aad_len;
             fr.index = jb.first_index + f;
             fr.len = uint32_t(plen);
-            fr.key = uint32_t(j);
+            fr.key = one_key ? 0u : uint32_t(j);
             fr.prefix_be = jb.prefix_be;
             frames.push_back(fr);
         }
@@ -257,6 +266,12 @@ int run_frames(Device& d, Slot& slot, hipStream_t s, const std::vector<Job>& job
         a.slot_stride = win->w.slot_stride;
         a.slots = win->w.slots;
         MXEC_HIP(launch_gcm_frames_window(a, decrypt, d.n_cus, s));
+    } else if (ring) {
+        GcmRingArgs ra{};
+        static_cast<GcmArgs&>(ra) = a;
+        ra.ring = ring->base_dev;
+        ra.ring_bytes = ring->bytes;
+        MXEC_HIP(launch_gcm_frames_ring(ra, d.n_cus, s));
     } else {
         MXEC_HIP(launch_gcm_frames(a, decrypt, d.n_cus, s));
     }
@@ -343,6 +358,47 @@ int mxec::gcm_decrypt_window(Device& d, Slot& slot, hipStream_t s, const GcmKey*
     const Job jb{q.key, 0, q.frame_size, q.first_index, q.aad_dev, q.aad_len, nullptr, q.len, q.out_dev};
     const Window win{w, stream_off};
     return run_frames(d, slot, s, {jb}, true, status_dev, key_dev, &win, arena);
+}
+
+// The argument checks of the ring form (include/maxio_ec.h
+// mxec_frames_decrypt_ring_device), all before anything is queued.
+int mxec::gcm_ring_check(const mxec_frames_job* jobs, uint64_t n_jobs, const uint64_t* ring_off,
+                         const mxec_frames_ring* ring, const int32_t* status_dev, bool need_key) {
+    if (n_jobs == 0) return MXEC_OK;
+    if (!jobs || !ring || !ring->base_dev || !ring_off) return set_error(MXEC_E_INVALID_ARG, "null argument");
+    if (ring->bytes == 0) return set_error(MXEC_E_INVALID_ARG, "ring bytes must be > 0");
+    uint64_t sum = 0;
+    for (uint64_t j = 0; j < n_jobs; ++j) {
+        const mxec_frames_job& q = jobs[j];
+        if ((need_key && !q.key) || (q.len && !q.in_dev) || (q.aad_len && !q.aad_dev))
+            return set_error(MXEC_E_INVALID_ARG, "null argument");
+        MXEC_TRY(check_frame_size(q.frame_size));
+        // The kernel's offsets within a frame are 32-bit.
+        if (q.frame_size > 0x7FFFFF00u) return set_error(MXEC_E_INVALID_ARG, "frame_size must be below 2^31 for a ring");
+        if (ring_off[j] >= ring->bytes)
+            return set_error(MXEC_E_INVALID_ARG, "ring_off " + std::to_string(ring_off[j]) + " is not below the ring's " +
+                                                     std::to_string(ring->bytes) + " bytes");
+        if (q.len && !status_dev) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        if (q.len > ring->bytes - sum)
+            return set_error(MXEC_E_INVALID_ARG, "the jobs' plaintext bytes exceed the ring's " +
+                                                     std::to_string(ring->bytes) + ": the call would overwrite itself");
+        sum += q.len;
+    }
+    return MXEC_OK;
+}
+
+// The ring form's launch (checked by gcm_ring_check), enqueue-only.  key_dev:
+// one GcmKey resident in HBM that every job runs under, or null to prepare
+// each job's q.key for this launch.
+int mxec::gcm_decrypt_ring(Device& d, Slot& slot, hipStream_t s, const GcmKey* key_dev, const mxec_frames_job* jobs,
+                           uint64_t n_jobs, const uint64_t* ring_off, const mxec_frames_ring& ring,
+                           int32_t* status_dev, DescArena* arena) {
+    std::vector<Job> js;
+    for (uint64_t j = 0; j < n_jobs; ++j) {
+        const mxec_frames_job& q = jobs[j];
+        js.push_back(Job{q.key, 0, q.frame_size, q.first_index, q.aad_dev, q.aad_len, q.in_dev, q.len, nullptr, ring_off[j]});
+    }
+    return run_frames(d, slot, s, js, true, status_dev, key_dev, nullptr, arena, &ring, key_dev != nullptr);
 }
 
 extern "C" {
@@ -465,6 +521,21 @@ int mxec_frames_decrypt_window_device(mxec_ctx* ctx, int dev, void* stream, cons
         MXEC_TRY(ds.open(ctx, dev));
         return gcm_decrypt_window(*ds.d, *ds.slot, static_cast<hipStream_t>(stream), nullptr, *job, stream_off, *win,
                                   frame_status_dev);
+    });
+}
+
+int mxec_frames_decrypt_ring_device(mxec_ctx* ctx, int dev, void* stream, const mxec_frames_job* jobs, uint64_t n_jobs,
+                                    const uint64_t* ring_off, const void* ring_, int32_t* frame_status_dev) {
+    return guarded([&] {
+        const auto* ring = static_cast<const mxec_frames_ring*>(ring_);
+        MXEC_TRY(gcm_ring_check(jobs, n_jobs, ring_off, ring, frame_status_dev, true));
+        uint64_t total = 0;
+        for (uint64_t j = 0; j < n_jobs; ++j) total += jobs[j].len;
+        if (total == 0) return MXEC_OK;
+        DevScope ds;
+        MXEC_TRY(ds.open(ctx, dev));
+        return gcm_decrypt_ring(*ds.d, *ds.slot, static_cast<hipStream_t>(stream), nullptr, jobs, n_jobs, ring_off, *ring,
+                                frame_status_dev);
     });
 }
 

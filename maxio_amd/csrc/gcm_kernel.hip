@@ -313,6 +313,34 @@ __device__ __forceinline__ u32x4 win_load(const WinFrame& w, uint32_t o, uint32_
     return win_load_bytes(w, c, n);
 }
 
+// ---- the plaintext ring (decrypt into it) ----
+// One frame's view of a byte ring, uniform over its 256 lanes (kept in SGPRs):
+// plaintext byte o of the frame lives at p + o while o < room and at pw + o
+// once the ring has wrapped (pw = p - ring bytes).  A frame is shorter than
+// the ring, so there is one wrap at the most.
+struct RingFrame {
+    uintptr_t p, pw;
+    uint32_t room;  // frame bytes in front of the wrap (clamped to 2^32 - 1: an uncut frame never asks)
+};
+// n (<= 16) bytes of v at frame offset o: one store when the wrap does not
+// fall inside them, byte by byte to either side of it otherwise.
+__device__ __forceinline__ void ring_store(const RingFrame& r, uint32_t o, u32x4 v, uint32_t n) {
+    if (o >= r.room || o + n <= r.room) {
+        uint8_t* p = reinterpret_cast<uint8_t*>((o >= r.room ? r.pw : r.p) + o);
+        if (n == 16) store16_be(p, v);
+        else store_partial_be(p, v, n);
+        return;
+    }
+#pragma unroll 1
+    for (uint32_t i = 0; i < n; ++i) {
+        *reinterpret_cast<uint8_t*>((o + i >= r.room ? r.pw : r.p) + o + i) = uint8_t(v.x >> 24);
+        v.x = __builtin_amdgcn_alignbit(v.x, v.y, 24);
+        v.y = __builtin_amdgcn_alignbit(v.y, v.z, 24);
+        v.z = __builtin_amdgcn_alignbit(v.z, v.w, 24);
+        v.w <<= 8;
+    }
+}
+
 // LDS: the four T-tables replicated 32 times, laid out so that a lookup's
 // address is ONE v_perm_b32 of the state word and a per-lane constant:
 //     byte offset = pair * 65536 + x * 256 + t * 128 + (lane % 32) * 4
@@ -347,9 +375,14 @@ typedef const uint32_t __attribute__((address_space(3)))* lds_u32p;
 // no chunk boundary cuts gets its pointers once and runs the contiguous form's
 // loads and stores; a cut frame sends every access to the stream through
 // win_store / win_load.  Which it is, is uniform and held in an SGPR.
-template <bool kDecrypt, bool kWindow = false>
+// kRing (decrypt): the frame stream is contiguous, as in the plain form, and
+// the plaintext goes into a byte ring (GcmRingArgs; GcmFrame::ring_off) in the
+// same manner: a frame the ring's wrap does not cut stores as the contiguous
+// form does, a cut one sends its plaintext stores through ring_store.
+template <bool kDecrypt, bool kWindow = false, bool kRing = false>
 __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
-    typename std::conditional<kWindow, GcmWinArgs, GcmArgs>::type a) {
+    typename std::conditional<kRing, GcmRingArgs, typename std::conditional<kWindow, GcmWinArgs, GcmArgs>::type>::type a) {
+    static_assert(!kRing || (kDecrypt && !kWindow), "the ring form is a decrypt form over a contiguous stream");
     extern __shared__ uint32_t smem[];
     uint32_t* te = smem;
     // The lookup addresses assume the tables start at LDS address 0.
@@ -410,14 +443,25 @@ __global__ __launch_bounds__(256 * kGcmGroups) void gcm_frames_kernel(
             else out_p = hdr_p + 12;
             tag_p = hdr_p + 12 + fr.len;
         }
+        RingFrame rf{};
+        if constexpr (kRing) {
+            const uint64_t room = a.ring_bytes - fr.ring_off;  // ring_off < ring_bytes
+            rf.p = uniform(uint64_t(reinterpret_cast<uintptr_t>(a.ring)) + fr.ring_off);
+            rf.pw = uniform(uint64_t(rf.p) - a.ring_bytes);
+            rf.room = uniform(uint32_t(min(room, uint64_t(0xFFFFFFFFu))));
+            cut = uniform(uint32_t(live && room < uint64_t(fr.len))) != 0;
+            out_p = reinterpret_cast<uint8_t*>(rf.p);
+        }
         constexpr bool kWinOut = kWindow && !kDecrypt, kWinIn = kWindow && kDecrypt;
         // 16 bytes, or the partial last block's n, of the payload at offset off.
         auto put16 = [&](uint32_t off, const u32x4& v) {
             if (kWinOut && cut) win_store(wf, 12 + off, v, 16);
+            else if (kRing && cut) ring_store(rf, off, v, 16);
             else store16_be(out_p + off, v);
         };
         auto putn = [&](uint32_t off, const u32x4& v, uint32_t n) {
             if (kWinOut && cut) win_store(wf, 12 + off, v, n);
+            else if (kRing && cut) ring_store(rf, off, v, n);
             else store_partial_be(out_p + off, v, n);
         };
         auto get16 = [&](uint32_t off) -> u32x4 {
@@ -603,6 +647,17 @@ hipError_t launch_gcm_frames_window(const GcmWinArgs& a, bool decrypt, int n_cus
     const dim3 grid(gcm_grid(a.n_frames, n_cus)), block(256 * kGcmGroups);
     if (decrypt) hipLaunchKernelGGL((gcm_frames_kernel<true, true>), grid, block, kGcmLdsBytes, s, a);
     else hipLaunchKernelGGL((gcm_frames_kernel<false, true>), grid, block, kGcmLdsBytes, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_gcm_frames_ring(const GcmRingArgs& a, int n_cus, hipStream_t s) {
+    if (a.n_frames == 0) return hipSuccess;
+    static const hipError_t attr =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gcm_frames_kernel<true, false, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, int(kGcmLdsBytes));
+    if (attr != hipSuccess) return attr;
+    const dim3 grid(gcm_grid(a.n_frames, n_cus)), block(256 * kGcmGroups);
+    hipLaunchKernelGGL((gcm_frames_kernel<true, false, true>), grid, block, kGcmLdsBytes, s, a);
     return hipGetLastError();
 }
 

@@ -206,7 +206,10 @@ struct GcmKey {
 };
 struct GcmFrame {
     const uint8_t* in;       // payload in (plaintext / ciphertext)
-    uint8_t* out;            // payload out
+    union {
+        uint8_t* out;        // payload out
+        uint64_t ring_off;   // ring form: where the frame's plaintext starts in the ring (< ring_bytes)
+    };
     union {
         uint8_t* hdr;        // encrypt: 12-byte nonce written here; decrypt: stored nonce
         uint64_t pos;        // window forms: the frame's byte offset in the frame stream, which is where
@@ -242,6 +245,17 @@ struct GcmWinArgs : GcmArgs {
     uint64_t chunk_size, slot_stride, slots;
 };
 hipError_t launch_gcm_frames_window(const GcmWinArgs& a, bool decrypt, int n_cus, hipStream_t s);
+// The decrypt form whose plaintext side is a byte ring: the frame stream is
+// contiguous (GcmFrame::hdr / in / tag as in launch_gcm_frames), plaintext
+// byte o of a frame is stored at ring + (ring_off + o) % ring_bytes, and the
+// frame's status goes to status[f].  A frame is no longer than the ring, so at
+// most one wrap cuts it; nothing outside [ring, ring + ring_bytes) and nothing
+// in it outside the frames' ranges is written.
+struct GcmRingArgs : GcmArgs {
+    uint8_t* ring;
+    uint64_t ring_bytes;
+};
+hipError_t launch_gcm_frames_ring(const GcmRingArgs& a, int n_cus, hipStream_t s);
 
 // ---- host <-> device copies by CU waves (copy_kernel.hip) ---------------------
 // One block of a copy batch: len bytes from src to dst (one side host memory

@@ -209,6 +209,9 @@ int run_body_sums(Device& d, Slot& slot, hipStream_t s, const std::vector<const 
 // gcm_decrypt_window: the same for mxec_frames_decrypt_window_device (checked
 // with decrypt = true: out_dev is then the contiguous side, in_dev ignored);
 // status_dev takes a status per frame, written on s like the plaintext.
+// gcm_ring_check / gcm_decrypt_ring: the checks and the launch of
+// mxec_frames_decrypt_ring_device, enqueue-only; key_dev = one resident
+// record that every job runs under (the jobs' keys are then not read).
 // gcm_frame_fail: MXEC_E_INTEGRITY with crypto.rs's text for a frame status
 // (2: index mismatch with both indices, else the authentication error).
 struct GcmKey;
@@ -220,6 +223,35 @@ int gcm_encrypt_window(Device& d, Slot& slot, hipStream_t s, const GcmKey* key_d
 int gcm_decrypt_window(Device& d, Slot& slot, hipStream_t s, const GcmKey* key_dev, const mxec_frames_job& q,
                        uint64_t stream_off, const mxec_frames_window& w, int32_t* status_dev,
                        DescArena* arena = nullptr);
+int gcm_ring_check(const mxec_frames_job* jobs, uint64_t n_jobs, const uint64_t* ring_off, const mxec_frames_ring* ring,
+                   const int32_t* status_dev, bool need_key);
+int gcm_decrypt_ring(Device& d, Slot& slot, hipStream_t s, const GcmKey* key_dev, const mxec_frames_job* jobs,
+                     uint64_t n_jobs, const uint64_t* ring_off, const mxec_frames_ring& ring, int32_t* status_dev,
+                     DescArena* arena = nullptr);
+
+// The device-side feed of an encrypted writer (storage_writer.cpp; not part of
+// the ABI): the frames of encrypted multipart parts, decrypted under the
+// upload key straight into the writer's plaintext ring.  writer_feed_key, once
+// after mxec_writer_open_encrypted: the upload key's tables, resident until
+// close.  writer_feed_frames: one launch step of part_plan.hpp's feed (planned
+// over writer_ring_bytes of the body), src[j] the file of step.jobs[j]'s part;
+// it takes the place of the mxec_writer_write of those plaintext bytes, may be
+// mixed with such writes in body order, and poisons the writer like them.  A
+// part frame that fails its check is MXEC_E_INTEGRITY with
+// mxec_frames_decrypt's texts, from a later feed call or from finish().
+struct FeedStep;
+struct WriterFeedSrc {
+    int fd;
+    const char* path;  // for messages
+    uint32_t part_number;
+};
+uint64_t writer_ring_bytes(uint64_t plain_len);
+int writer_feed_key(void* writer, const uint8_t* upload_key, const char* upload_id);
+int writer_feed_frames(void* writer, const FeedStep& step, const WriterFeedSrc* src);
+
+// The multipart ETag (filesystem.rs:1240-1244): MD5 over the parts' raw MD5s,
+// "-N" (storage_multipart.cpp).
+int multipart_etag(mxec_ctx* ctx, const mxec_multipart_part* parts, uint32_t n_parts, char* etag_out);
 
 // Creates the device's host-pipeline hub and its streams (pipe_hub.cpp),
 // called by mxec_open for every device.

@@ -234,16 +234,6 @@ int read_parts(mxec_ctx* ctx, const mxec_multipart_part* parts, uint32_t n_parts
     return MXEC_OK;
 }
 
-// The multipart ETag (:1240-1244): MD5 over the parts' raw MD5s, "-N".
-int multipart_etag(mxec_ctx* ctx, const mxec_multipart_part* parts, uint32_t n_parts, char* etag_out) {
-    std::vector<uint8_t> md5s(size_t(n_parts) * 16 + 1);
-    for (uint32_t p = 0; p < n_parts; ++p) std::memcpy(&md5s[size_t(p) * 16], parts[p].md5, 16);
-    mxec_body_sums sums;
-    MXEC_TRY(body_sums(ctx, md5s.data(), size_t(n_parts) * 16, MXEC_SUM_MD5, &sums));
-    std::snprintf(etag_out, 48, "%s-%u", hex(sums.md5, 16).c_str(), n_parts);
-    return MXEC_OK;
-}
-
 }  // namespace
 
 extern "C" {

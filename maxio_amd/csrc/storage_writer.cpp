@@ -36,6 +36,19 @@
 // body digests run over the plaintext ring, one run per stretch.  A stretch is
 // reused once its launch and its digest run have finished, a slot once its
 // chunk's hash, fold and download have.
+//
+// The device-side feed (writer_feed_key / writer_feed_frames, ops.hpp; the
+// streaming CompleteMultipartUpload of storage_multipart.cpp): the frames of
+// encrypted multipart parts, 16 at a time (part_plan.hpp's launches), are read
+// from the part files into one of two page-locked pieces, go up into one of
+// two stretches of a ciphertext bounce, and one launch of the GCM kernel's
+// ring form on the main stream decrypts them under the upload key straight
+// into the plaintext ring at the body offset; `written` advances and the
+// encrypt launches that are then due follow in stream order, exactly as after
+// an upload.  A stretch of the ring is waited for as enc_write waits for it.
+// The frame statuses come down behind each launch and are checked no later
+// than the next reuse of their bounce stretch, all of them in finish() before
+// a parity file or the manifest is written.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -44,6 +57,7 @@
 
 #include "frame_plan.hpp"
 #include "kernels.hpp"
+#include "part_plan.hpp"
 #include "ops.hpp"
 #include "sha256_host.hpp"
 #include "shard_files.hpp"
@@ -87,6 +101,41 @@ struct DownPiece {
     hipEvent_t landed = nullptr;
     uint64_t off = 0, len = 0;
 };
+// The plaintext ring's bytes for a body: the whole of a body within one
+// stretch, else one stretch per MiB up to kRingRuns.
+uint64_t ring_bytes_for(uint64_t plain_len) {
+    const uint64_t runs = std::min<uint64_t>(kRingRuns, enc_run_count(plain_len));
+    return runs <= 1 ? std::max<uint64_t>(plain_len, 256) : runs * kEncRun;
+}
+
+// One launch of the device-side feed in flight: its part frames on the host,
+// its statuses, and what a failed frame's message needs.
+constexpr int kFeedBounces = 2;
+struct FeedBounce {
+    PinnedBuf ct, st;           // the frames, job after job | their statuses, landed
+    hipEvent_t done = nullptr;  // ... behind the launch on the main stream
+    bool busy = false;
+    DescArena tables;
+    uint32_t frames = 0;
+    uint64_t expect[kFeedFrames];  // each frame's index in its part
+    uint64_t hdr_at[kFeedFrames];  // ... and where its stored nonce lies in ct
+};
+struct FeedState {
+    uint8_t key[32];
+    GcmKey tables;  // the host copy of what key_dev holds
+    DevBuf key_dev;
+    std::string aad_prefix;         // "PART" 0 upload_id 0 (part_aad_builder, filesystem.rs:147-163)
+    uint64_t ring_bytes = 0;
+    DevBuf ct_dev, aad_dev, st_dev;  // kFeedBounces * (kEncRunStream | kFeedFrames * 32 | kFeedFrames * 4)
+    PinnedBuf aad_host;
+    FeedBounce b[kFeedBounces];
+    uint64_t next = 0;
+    ~FeedState() {  // the upload key does not outlive the writer on the host
+        explicit_bzero(key, sizeof key);
+        explicit_bzero(&tables, sizeof tables);
+    }
+};
+
 struct EncState {
     uint64_t plain_len = 0;
     WriterPlan pplan;  // the plaintext as one body: the over-run and short-finish texts are in its bytes
@@ -102,6 +151,7 @@ struct EncState {
     DownPiece down[kDownPieces];
     uint64_t down_head = 0, down_next = 0;  // pieces gone to their files | queued
     uint64_t filed = 0;                     // stream bytes in the chunk files
+    std::unique_ptr<FeedState> feed;        // writer_feed_key; null otherwise
 
     uint8_t* ring_ptr(uint64_t run) const { return static_cast<uint8_t*>(ring.p) + (run % kRingRuns) * kEncRun; }
     size_t aad_at(uint64_t run) const { return size_t(run % kRingRuns) * kEncFrames * 32; }
@@ -187,6 +237,11 @@ struct mxec_writer {
             for (DownPiece& p : enc->down)
                 if (p.landed) (void)hipEventDestroy(p.landed);
             if (enc->key_dev.p) (void)hipMemset(enc->key_dev.p, 0, sizeof(GcmKey));
+            if (enc->feed) {
+                for (FeedBounce& fb : enc->feed->b)
+                    if (fb.done) (void)hipEventDestroy(fb.done);
+                if (enc->feed->key_dev.p) (void)hipMemset(enc->feed->key_dev.p, 0, sizeof(GcmKey));
+            }
         }
         for (WindowSlot& w : slots) {
             if (w.summed) (void)hipEventDestroy(w.summed);
@@ -516,7 +571,122 @@ int enc_write(mxec_writer& w, const uint8_t* buf, uint64_t len) {
     return MXEC_OK;
 }
 
+// ---- the device-side feed ---------------------------------------------------------------------------
+
+// The bounce stretch's launch has finished: its frames' statuses, the first
+// bad one as mxec_frames_decrypt words it.
+int feed_settle(FeedBounce& fb) {
+    if (!fb.busy) return MXEC_OK;
+    MXEC_HIP(hipEventSynchronize(fb.done));
+    fb.busy = false;
+    const int32_t* st = static_cast<const int32_t*>(fb.st.p);
+    for (uint32_t f = 0; f < fb.frames; ++f) {
+        if (st[f] == 0) continue;
+        uint64_t got = 0;  // the stored index: nonce bytes 4..11, LE
+        const uint8_t* h = static_cast<const uint8_t*>(fb.ct.p) + fb.hdr_at[f] + 4;
+        for (int j = 7; j >= 0; --j) got = (got << 8) | h[j];
+        return gcm_frame_fail(st[f], fb.expect[f], got);
+    }
+    return MXEC_OK;
+}
+
+int read_at(int fd, uint8_t* dst, uint64_t len, uint64_t off, const char* path) {
+    while (len) {
+        const ssize_t n = ::pread(fd, dst, size_t(len), off_t(off));
+        if (n < 0 && errno == EINTR) continue;
+        if (n <= 0) return set_error(MXEC_E_IO, std::string("IO error: read failed for ") + (path ? path : "part file"));
+        dst += n;
+        off += uint64_t(n);
+        len -= uint64_t(n);
+    }
+    return MXEC_OK;
+}
+
+// One launch of part_plan.hpp: its frames from the part files into the ring
+// at the body offset, then whatever encrypt launches are due.
+int feed_launch(mxec_writer& w, const FeedStep& L, const WriterFeedSrc* src) {
+    EncState& e = *w.enc;
+    FeedState& fs = *e.feed;
+    if (!L.launch || L.n_jobs == 0 || L.n_jobs > kFeedFrames || L.frames == 0 || L.frames > kFeedFrames ||
+        L.body_off != w.written || L.body_end < L.body_off || L.body_end > e.plain_len)
+        return set_error(MXEC_E_INVALID_ARG, "feed step out of order at plaintext byte " + std::to_string(w.written));
+    const uint64_t bi = fs.next % kFeedBounces;
+    FeedBounce& fb = fs.b[bi];
+    MXEC_TRY(feed_settle(fb));  // the stretch's last launch: its statuses before its frames go
+    uint8_t* ct = static_cast<uint8_t*>(fb.ct.p);
+    uint8_t* ct_dev = static_cast<uint8_t*>(fs.ct_dev.p) + bi * kEncRunStream;
+    uint8_t* ah = static_cast<uint8_t*>(fs.aad_host.p) + bi * kFeedFrames * 32;
+    uint8_t* ad = static_cast<uint8_t*>(fs.aad_dev.p) + bi * kFeedFrames * 32;
+    int32_t* st_dev = static_cast<int32_t*>(fs.st_dev.p) + bi * kFeedFrames;
+    mxec_frames_job jobs[kFeedFrames];
+    uint64_t ring_off[kFeedFrames];
+    uint64_t at = 0, body = L.body_off;
+    uint32_t nf = 0;
+    std::vector<uint8_t> msg;
+    for (uint32_t j = 0; j < L.n_jobs; ++j) {
+        const FeedJob& q = L.jobs[j];
+        if (q.frames == 0 || nf + q.frames > L.frames || q.plain_bytes == 0 || q.plain_bytes > q.frames * kFramePlain ||
+            q.stream_bytes != q.plain_bytes + kFrameExtra * q.frames || q.ring_off != body % fs.ring_bytes ||
+            q.plain_bytes > L.body_end - body)
+            return set_error(MXEC_E_INVALID_ARG, "feed step does not match the writer's ring");
+        MXEC_TRY(read_at(src[j].fd, ct + at, q.stream_bytes, q.file_off, src[j].path));
+        // Frame i's AAD = SHA-256("PART" 0 upload_id 0 part_number_le4 0 || i as u64 LE) (:147-163).
+        msg.assign(fs.aad_prefix.begin(), fs.aad_prefix.end());
+        for (int b = 0; b < 4; ++b) msg.push_back(uint8_t(src[j].part_number >> (8 * b)));
+        msg.push_back(0);
+        const size_t pl = msg.size();
+        msg.resize(pl + 8);
+        mxec_frames_job& jb = jobs[j];
+        jb = mxec_frames_job{};
+        jb.frame_size = uint32_t(kFramePlain);
+        jb.first_index = q.first_frame;
+        jb.aad_dev = ad + size_t(nf) * 32;
+        jb.aad_len = 32;
+        jb.in_dev = ct_dev + at;
+        jb.len = q.plain_bytes;
+        ring_off[j] = q.ring_off;
+        for (uint64_t f = 0; f < q.frames; ++f, ++nf) {
+            for (int b = 0; b < 8; ++b) msg[pl + size_t(b)] = uint8_t((q.first_frame + f) >> (8 * b));
+            sha256_host(msg.data(), msg.size(), ah + size_t(nf) * 32);
+            fb.expect[nf] = q.first_frame + f;
+            fb.hdr_at[nf] = at + f * kFrameBytes;
+        }
+        at += q.stream_bytes;
+        body += q.plain_bytes;
+    }
+    if (nf != L.frames || body != L.body_end) return set_error(MXEC_E_INVALID_ARG, "feed step does not match the writer's ring");
+    // Back-pressure: a stretch the launch opens must be done with its last
+    // tenant (its encrypt launch, its digest run), as in enc_write.
+    for (uint64_t r = L.open_first; r < L.open_first + L.open_count; ++r) {
+        RingRun& rr = e.runs[r % kRingRuns];
+        if (rr.busy) MXEC_HIP(hipEventSynchronize(rr.encrypted));
+        if (rr.sum_busy) MXEC_HIP(hipEventSynchronize(rr.summed));
+        rr.busy = rr.sum_busy = false;
+    }
+    MXEC_HIP(hipMemcpyAsync(ct_dev, ct, size_t(at), hipMemcpyHostToDevice, w.s));
+    MXEC_HIP(hipMemcpyAsync(ad, ah, size_t(nf) * 32, hipMemcpyHostToDevice, w.s));
+    const mxec_frames_ring ring{static_cast<uint8_t*>(e.ring.p), fs.ring_bytes};
+    {
+        DevScope ds;
+        MXEC_TRY(ds.open(w.ctx, w.dev_index));
+        MXEC_TRY(gcm_ring_check(jobs, L.n_jobs, ring_off, &ring, st_dev, false));
+        MXEC_TRY(fb.tables.reserve(4096));
+        MXEC_TRY(gcm_decrypt_ring(*ds.d, *ds.slot, w.s, static_cast<const GcmKey*>(fs.key_dev.p), jobs, L.n_jobs, ring_off,
+                                  ring, st_dev, &fb.tables));
+    }
+    MXEC_HIP(hipMemcpyAsync(fb.st.p, st_dev, size_t(nf) * sizeof(int32_t), hipMemcpyDeviceToHost, w.s));
+    MXEC_HIP(hipEventRecord(fb.done, w.s));
+    fb.busy = true;
+    fb.frames = nf;
+    ++fs.next;
+    const uint64_t from = w.written;
+    w.written = L.body_end;
+    return enc_runs_due(e.plain_len, from, w.written, [&](const EncRun& q) { return queue_enc_run(w, q); });
+}
+
 int finish(mxec_writer& w) {
+    if (w.enc && w.enc->feed)  // no parity file and no manifest over a part frame that failed
+        for (FeedBounce& fb : w.enc->feed->b) MXEC_TRY(feed_settle(fb));
     if (w.enc) {
         if (w.written != w.enc->plain_len)
             return set_error(MXEC_E_INVALID_ARG, writer_short_msg(w.enc->pplan, w.written));
@@ -586,8 +756,7 @@ int open_enc(mxec_writer& w, const EncOpen& eo) {
     gcm_prepare_key(e.key, e.tables);
     MXEC_TRY(e.key_dev.ensure(sizeof(GcmKey)));
     MXEC_HIP(hipMemcpy(e.key_dev.p, &e.tables, sizeof(GcmKey), hipMemcpyHostToDevice));
-    const uint64_t runs = std::min<uint64_t>(kRingRuns, enc_run_count(eo.plain_len));
-    MXEC_TRY(e.ring.ensure(size_t(runs <= 1 ? std::max<uint64_t>(eo.plain_len, 256) : runs * kEncRun)));
+    MXEC_TRY(e.ring.ensure(size_t(ring_bytes_for(eo.plain_len))));
     MXEC_TRY(e.aad_dev.ensure(size_t(kRingRuns * kEncFrames * 32)));
     MXEC_TRY(e.aad_host.ensure(size_t(kRingRuns * kEncFrames * 32)));
     for (RingRun& r : e.runs) {
@@ -690,6 +859,49 @@ int open_writer(mxec_ctx* ctx, const char* ec_dir, uint64_t chunk_size, uint32_t
 }
 
 }  // namespace
+
+// The plaintext ring an encrypted writer of plain_len bytes has (part_plan.hpp's ring_bytes).
+uint64_t mxec::writer_ring_bytes(uint64_t plain_len) { return ring_bytes_for(plain_len); }
+
+int mxec::writer_feed_key(void* wp, const uint8_t* upload_key, const char* upload_id) {
+    return guarded([&]() -> int {
+        auto* w = static_cast<mxec_writer*>(wp);
+        if (!w || !w->enc || !upload_key || !upload_id) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        if (w->err) return set_error(w->err, w->err_msg);
+        if (w->enc->feed) return set_error(MXEC_E_INVALID_ARG, "the feed's key is already set");
+        MXEC_HIP(hipSetDevice(w->dev->id));
+        w->enc->feed = std::make_unique<FeedState>();  // the writer's close takes it from here on
+        FeedState& fs = *w->enc->feed;
+        std::memcpy(fs.key, upload_key, 32);
+        fs.aad_prefix = std::string("PART") + '\0' + upload_id + '\0';
+        fs.ring_bytes = ring_bytes_for(w->enc->plain_len);
+        gcm_prepare_key(fs.key, fs.tables);
+        MXEC_TRY(fs.key_dev.ensure(sizeof(GcmKey)));
+        MXEC_HIP(hipMemcpy(fs.key_dev.p, &fs.tables, sizeof(GcmKey), hipMemcpyHostToDevice));
+        MXEC_TRY(fs.ct_dev.ensure(size_t(kFeedBounces * kEncRunStream)));
+        MXEC_TRY(fs.aad_dev.ensure(size_t(kFeedBounces * kFeedFrames * 32)));
+        MXEC_TRY(fs.aad_host.ensure(size_t(kFeedBounces * kFeedFrames * 32)));
+        MXEC_TRY(fs.st_dev.ensure(size_t(kFeedBounces * kFeedFrames * sizeof(int32_t))));
+        for (FeedBounce& fb : fs.b) {
+            MXEC_TRY(fb.ct.ensure(size_t(kEncRunStream)));
+            MXEC_TRY(fb.st.ensure(size_t(kFeedFrames * sizeof(int32_t))));
+            MXEC_TRY(new_event(&fb.done));
+            fb.tables.owner = w->dev;
+        }
+        return MXEC_OK;
+    });
+}
+
+int mxec::writer_feed_frames(void* wp, const FeedStep& step, const WriterFeedSrc* src) {
+    return guarded([&]() -> int {
+        auto* w = static_cast<mxec_writer*>(wp);
+        if (!w || !w->enc || !w->enc->feed || !src) return set_error(MXEC_E_INVALID_ARG, "null argument");
+        if (w->err) return set_error(w->err, w->err_msg);
+        if (w->finished) return set_error(MXEC_E_INVALID_ARG, "write after finish");
+        MXEC_HIP(hipSetDevice(w->dev->id));
+        return poison(*w, feed_launch(*w, step, src));
+    });
+}
 
 extern "C" {
 

@@ -792,6 +792,32 @@ class Context:
             upload_id.encode(), _ptr(k), _ptr(pre), _ptr(ap) if ap.size else None, ap.size, etag))
         return '"' + etag.value.decode() + '"'
 
+    def complete_multipart_streamed(self, ec_dir: str, chunk_size: int, parity_shards: int,
+                                    parts: Sequence[dict], window_bytes: int = 0) -> str:
+        """complete_multipart_chunked as a stream (mxec_complete_multipart_streamed):
+        the parts go through a chunk writer in pieces, none is buffered; the
+        same files, manifest and ETag.  window_bytes: the writer's, 0 = default."""
+        etag = ctypes.create_string_buffer(48)
+        _check(self._lib.mxec_complete_multipart_streamed(self._h, ec_dir.encode(), chunk_size, parity_shards,
+                                                          self._parts(parts), len(parts), window_bytes, etag))
+        return '"' + etag.value.decode() + '"'
+
+    def complete_multipart_streamed_encrypted(self, ec_dir: str, chunk_size: int, parity_shards: int,
+                                              parts: Sequence[dict], upload_key: Optional[bytes],
+                                              upload_id: Optional[str], key: bytes, nonce_prefix: bytes,
+                                              aad_prefix: bytes, window_bytes: int = 0) -> str:
+        """complete_multipart_chunked_encrypted as a stream
+        (mxec_complete_multipart_streamed_encrypted): encrypted parts are
+        decrypted in HBM straight into the encrypted writer's plaintext ring."""
+        etag = ctypes.create_string_buffer(48)
+        uk = _u8(upload_key) if upload_key is not None else None
+        k, pre, ap = _u8(key), _u8(nonce_prefix), _u8(aad_prefix)
+        _check(self._lib.mxec_complete_multipart_streamed_encrypted(
+            self._h, ec_dir.encode(), chunk_size, parity_shards, self._parts(parts), len(parts),
+            _ptr(uk) if uk is not None else None, upload_id.encode() if upload_id is not None else None, _ptr(k),
+            _ptr(pre), _ptr(ap) if ap.size else None, ap.size, window_bytes, etag))
+        return '"' + etag.value.decode() + '"'
+
     # ---- encrypt-then-EC frames (storage/crypto.rs) ----------------------------
     def frames_encrypt(self, key: bytes, nonce_prefix: bytes, pt, aads: Optional[Sequence[bytes]] = None,
                        first_index: int = 0, frame_size: int = FRAME_CHUNK_SIZE) -> bytes:
@@ -892,6 +918,32 @@ class Context:
         win = N.FramesWindow(base_dev or None, chunk_size, slot_stride, slots)
         _check(self._lib.mxec_frames_decrypt_window_device(self._h, dev, stream, ctypes.byref(j), stream_off,
                                                            ctypes.byref(win), status_dev or None))
+
+    def frames_decrypt_ring_device(self, jobs: Sequence[dict], ring_offs: Sequence[int], base_dev: int,
+                                   ring_bytes: int, status_dev: int, dev: int = 0, stream=None) -> None:
+        """mxec_frames_decrypt_ring_device: jobs (dicts as frames_device takes;
+        out_dev and nonce_prefix are ignored) whose contiguous frame streams
+        at in_dev are decrypted into the byte ring of ring_bytes at base_dev,
+        job j's plaintext from ring_offs[j] on, modulo the ring; one int32
+        status per frame (0 ok, 1 tag, 2 index), in job order, to status_dev.
+        Enqueue-only."""
+        arr = (N.FramesJob * max(1, len(jobs)))()
+        keep = []
+        for i, j in enumerate(jobs):
+            k = _u8(j["key"]) if j.get("key") is not None else None
+            keep.append(k)
+            arr[i].key = _ptr(k) if k is not None else None
+            arr[i].frame_size = j.get("frame_size", FRAME_CHUNK_SIZE)
+            arr[i].first_index = j.get("first_index", 0)
+            arr[i].aad_dev = j.get("aad_dev") or None
+            arr[i].aad_len = j.get("aad_len", 0)
+            arr[i].in_dev = j.get("in_dev") or None
+            arr[i].len = j["len"]
+            arr[i].out_dev = None
+        offs = (ctypes.c_uint64 * max(1, len(ring_offs)))(*ring_offs) if ring_offs is not None else None
+        ring = N.FramesRing(base_dev or None, ring_bytes)
+        _check(self._lib.mxec_frames_decrypt_ring_device(self._h, dev, stream, arr if jobs is not None else None,
+                                                         len(jobs), offs, ctypes.byref(ring), status_dev or None))
 
     def frame_aads(self, prefix: bytes, first_index: int, n: int) -> list[bytes]:
         """build_frame_aad for frames first_index .. first_index + n - 1."""

@@ -92,6 +92,15 @@ pub struct MxecFramesWindow {
     pub slots: u64,
 }
 
+/// `mxec_frames_ring`: the byte ring that the ring form of the frame decryptor
+/// stores plaintext into (byte o of a job at `base_dev + (ring_off + o) % bytes`).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct MxecFramesRing {
+    pub base_dev: *mut u8,
+    pub bytes: u64,
+}
+
 /// `mxec_multipart_part`: one part of CompleteMultipartUpload (PartMeta).
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -285,6 +294,8 @@ extern "C" {
     /// `win`: a `*const MxecFramesWindow`.
     pub fn mxec_frames_encrypt_window_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, job: *const MxecFramesJob, stream_off: u64, win: *const c_void) -> c_int;
     pub fn mxec_frames_decrypt_window_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, job: *const MxecFramesJob, stream_off: u64, win: *const c_void, frame_status_dev: *mut i32) -> c_int;
+    /// `ring`: a `*const MxecFramesRing`; `ring_off`: one offset per job.
+    pub fn mxec_frames_decrypt_ring_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, jobs: *const MxecFramesJob, n_jobs: u64, ring_off: *const u64, ring: *const c_void, frame_status_dev: *mut i32) -> c_int;
     pub fn mxec_frames_decrypt_device(ctx: *mut MxecCtx, dev: c_int, stream: *mut c_void, jobs: *const MxecFramesJob, n_jobs: u64, status_out: *mut i32) -> c_int;
     pub fn mxec_frame_aads(ctx: *mut MxecCtx, prefix: *const u8, prefix_len: u32, first_index: u64, n_frames: u64, out: *mut [u8; 32]) -> c_int;
     pub fn mxec_body_sums_batch(ctx: *mut MxecCtx, bodies: *const *const u8, lens: *const u64, n: u64, which: u32, out: *mut MxecBodySums) -> c_int;
@@ -295,6 +306,8 @@ extern "C" {
     pub fn mxec_put_object_chunked_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, key: *const u8, nonce_prefix: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, body: *const u8, len: usize, which: u32, sums_out: *mut MxecBodySums) -> c_int;
     pub fn mxec_complete_multipart_chunked(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, parts: *const MxecMultipartPart, n_parts: u32, etag_out: *mut c_char) -> c_int;
     pub fn mxec_complete_multipart_chunked_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, parts: *const MxecMultipartPart, n_parts: u32, upload_key: *const u8, upload_id: *const c_char, key: *const u8, nonce_prefix: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, etag_out: *mut c_char) -> c_int;
+    pub fn mxec_complete_multipart_streamed(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, parts: *const MxecMultipartPart, n_parts: u32, window_bytes: u64, etag_out: *mut c_char) -> c_int;
+    pub fn mxec_complete_multipart_streamed_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, parts: *const MxecMultipartPart, n_parts: u32, upload_key: *const u8, upload_id: *const c_char, key: *const u8, nonce_prefix: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, window_bytes: u64, etag_out: *mut c_char) -> c_int;
     pub fn mxec_get_object_chunked(ctx: *mut MxecCtx, ec_dir: *const c_char, offset: u64, length: u64, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
     pub fn mxec_get_object_chunked_encrypted(ctx: *mut MxecCtx, ec_dir: *const c_char, key: *const u8, aad_prefix: *const u8, aad_prefix_len: u32, frame_size: u32, plaintext_size: u64, offset: u64, length: u64, out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
     pub fn mxec_writer_open(ctx: *mut MxecCtx, ec_dir: *const c_char, chunk_size: u64, parity_shards: u32, total_len: u64, plaintext_size: u64, window_bytes: u64, out: *mut *mut c_void) -> c_int;
