@@ -23,6 +23,7 @@ LAST_BLOCK = (16, 1, 15)
 SMALL_LENS = (1, 15, 16, 17)
 INDICES = (0, 2**32 - 1, 2**32, 2**40 + 3, 0x0102030405060708, 2**64 - 1)
 COUNTER_EDGE_BLOCKS = 65534  # the longest frame whose counters 2 + j stay below 2^16
+LONG_COUNTER_BLOCKS = 65535  # the shortest frame with a counter of 2^16: the long-counter AES path
 
 
 class Job(NamedTuple):
@@ -129,6 +130,54 @@ def counter_edge_case() -> Job:
     rng = np.random.default_rng(0x63747265)
     fs = COUNTER_EDGE_BLOCKS * 16
     return _job(rng, _bytes(rng, 32), 3, fs, 2**32 - 1, 17, fs + 16 * 300 + 5)
+
+
+@functools.lru_cache(maxsize=None)
+def long_counter_case() -> Job:
+    """A first frame of exactly 65535 blocks, the first whose last counter
+    (0x10000) leaves the two low counter bytes, and a short second one; a
+    17-byte AAD, the index carrying into its high word between them."""
+    rng = np.random.default_rng(0x6C6F6E67)
+    fs = LONG_COUNTER_BLOCKS * 16
+    return _job(rng, _bytes(rng, 32), 1, fs, 2**32 - 1, 17, fs + 16 * 41 + 9)
+
+
+def key_pass_cases(cus: int) -> tuple:
+    """tiny_cases(2 * 4 * cus + 37) with eight long frames at the start of each
+    of the three grid-stride passes of a full chip (jobs 0 .. 7, 4 cus .. 4 cus
+    + 7, 8 cus .. 8 cus + 7: workgroups 0 and 1, four frames each), so that a
+    frame group meets a long frame under another key in every pass.  A frame
+    of m <= 256 GHASH blocks never multiplies by H^256 (each lane folds one
+    block into a zero accumulator), so the tiny frames alone cannot tell a
+    stale H^256 table from a fresh one; these have m >= 258."""
+    lane = lane_cases()
+    long_ones = [j for j in lane if (j.aad_len + 15) // 16 + (len(j.pt) + 15) // 16 + 1 >= 258]
+    jobs = list(tiny_cases(2 * 4 * cus + 37))
+    for p in range(3):
+        for t in range(8):
+            k = 37 * p + 5 * t
+            while p and long_ones[k % len(long_ones)].key == jobs[4 * cus * (p - 1) + t].key:
+                k += 1
+            jobs[4 * cus * p + t] = long_ones[k % len(long_ones)]
+    return tuple(jobs)
+
+
+def flips(job: Job) -> list:
+    """(what, byte offset in the frame or the AAD, bit) of a single frame job:
+    the tamper positions of test_gcm_edges_gpu.py and test_gcm_form_edges_gpu.py."""
+    ln = len(job.pt)
+    at = [("prefix", 0), ("prefix", 3)] + [("index", b) for b in range(4, 12)]
+    at += [("ciphertext", 12), ("ciphertext", 12 + ln - 1), ("tag", 12 + ln), ("tag", 12 + ln + 15)]
+    at += [("aad", 0), ("aad", job.aad_len - 1)]
+    return [(what, off, 1 << (k % 8)) for k, (what, off) in enumerate(at)]
+
+
+def tamper_picks() -> list:
+    """The lane cases that get tampered with: AADs of 1, 2 and 257 blocks, a
+    partial last block, an index with a non-zero high word."""
+    lane = lane_cases()
+    return [next(i for i, j in enumerate(lane) if j.aad_len == aad_len and len(j.pt) > 16
+                 and len(j.pt) % 16 and j.first_index >= 2**32) for aad_len in (1, 17, 4101)]
 
 
 def frame_slices(job: Job):

@@ -169,13 +169,7 @@ def test_counter_boundary_frame(ctx):
     assert ctx.frames_decrypt(job.key, got, len(job.pt), **job.oracle_args()) == job.pt
 
 
-def _flips(job):
-    """(what, byte offset in the frame or the AAD, bit) of a single frame job."""
-    ln = len(job.pt)
-    at = [("prefix", 0), ("prefix", 3)] + [("index", b) for b in range(4, 12)]
-    at += [("ciphertext", 12), ("ciphertext", 12 + ln - 1), ("tag", 12 + ln), ("tag", 12 + ln + 15)]
-    at += [("aad", 0), ("aad", job.aad_len - 1)]
-    return [(what, off, 1 << (k % 8)) for k, (what, off) in enumerate(at)]
+_flips = gcm_cases.flips  # shared with test_gcm_form_edges_gpu.py
 
 
 def test_tamper_positions(ctx, sweep):
@@ -184,10 +178,7 @@ def test_tamper_positions(ctx, sweep):
     import torch
 
     lane = gcm_cases.lane_cases()
-    picks = []
-    for aad_len in (1, 17, 4101):
-        picks.append(next(i for i, j in enumerate(lane) if j.aad_len == aad_len and len(j.pt) > 16
-                          and len(j.pt) % 16 and j.first_index >= 2**32))
+    picks = gcm_cases.tamper_picks()
     frames_host = sweep.check_frames()
     # jobs: clean, flipped, clean, flipped, ..., clean; each on its own copy
     entries = [(i, flip) for i in picks for flip in _flips(lane[i])]

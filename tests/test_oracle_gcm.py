@@ -122,6 +122,16 @@ def test_counter_boundary_frame_matches_openssl():
     _check_job_against_openssl(job)
 
 
+@needs_openssl
+def test_long_counter_frame_matches_openssl():
+    """One frame of 65535 blocks: the last counter is 0x10000, the first that
+    the kernel's short-counter path cannot make."""
+    job = gcm_cases.long_counter_case()
+    assert job.n_frames == 2 and job.frame_size == 65535 * 16 and job.aad_len == 17
+    assert job.first_index < 2**32 <= job.first_index + 1
+    _check_job_against_openssl(job)
+
+
 def test_case_table_shape():
     """The table holds what the sweep relies on: every (na, m, last block)
     combination, single frames, and the byte-equal keys in two buffers."""
